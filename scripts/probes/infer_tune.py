@@ -9,7 +9,7 @@ rows = sys.argv[1] if len(sys.argv) > 1 else "100000000"
 for w in ("8", "12", "16"):
     env = dict(os.environ, HFENS_STACK_WAVES=w)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "infer", "--rows", rows,
-                        "--steps", "5", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=300)
+                        "--steps", "5", "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=300)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not line:
         print(w, "FAILED", r.stderr[-2000:])
