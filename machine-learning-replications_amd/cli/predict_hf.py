@@ -4,7 +4,8 @@ Same no-argument contract as the reference ``predict_hf.py:1-40``: the 17 clinic
 inputs (ordered as the model's columns, ``predict_hf.py:5-27``) default to the
 shipped example patient and the probability is printed between ``#`` rules.
 Additions: ``--set NAME=VALUE`` overrides, ``--csv`` batched scoring, ``--device``
-(``cuda`` runs the gfx950 kernels), ``--model`` path.
+(``cuda`` runs the gfx950 kernels), ``--model`` path, ``--explain [--background CSV]``
+(exact Shapley contribution of every variable, printed after the unchanged probability block).
 """
 from __future__ import annotations
 
@@ -51,12 +52,43 @@ def predict_patient(params=None, model_path=None, device="cpu") -> float:
     return float(p[0, 1])
 
 
+def _explainer(a):
+    from ..explain import StackExplainer
+    from ..io.checkpoint import load_checkpoint
+    bg = np.loadtxt(a.background, delimiter=",", ndmin=2) if a.background else None
+    return StackExplainer(load_checkpoint(a.model, device=a.device), bg, device=a.device,
+                          feature_names=list(PATIENT_PARAMS))
+
+
+def format_explanation(names, values, phi, base: float, pred: float) -> str:
+    """Base value, one line per variable (name, value, phi in percentage points) sorted by
+    |phi|, and the sum check ``Σ phi = prediction − base``."""
+    lines = [f"Base value (mean risk of the background cohort): {100 * base:.2f} %",
+             "Contribution of each variable (percentage points):"]
+    for k in sorted(range(len(names)), key=lambda k: -abs(phi[k])):
+        lines.append(f"  {names[k]:<24s} {values[k]:>8g} {100 * phi[k]:+10.4f}")
+    lines.append(f"Sum of contributions: {100 * sum(phi):+.4f} = {100 * pred:.4f} - {100 * base:.4f}")
+    return "\n".join(lines)
+
+
+def format_importance(names, mean_abs) -> str:
+    lines = ["Mean |contribution| of each variable over the cohort (percentage points):"]
+    for k in sorted(range(len(names)), key=lambda k: -mean_abs[k]):
+        lines.append(f"  {names[k]:<24s} {100 * mean_abs[k]:10.4f}")
+    return "\n".join(lines)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--model", default=None, help="checkpoint path (default: assets/hf_predict_model.pkl)")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE")
     ap.add_argument("--csv", default=None, help="score every row of a CSV with the 17 columns")
     ap.add_argument("--device", default="cpu")
+    ap.add_argument("--explain", action="store_true",
+                    help="exact Shapley contribution of every variable (with --csv: mean |contribution|)")
+    ap.add_argument("--background", default=None, metavar="CSV",
+                    help="background cohort for --explain (default: 128 synthetic HF patients; "
+                         "on --device cpu each background row costs seconds per patient)")
     a = ap.parse_args(argv)
     if a.csv:
         from ..io.checkpoint import load_checkpoint
@@ -65,6 +97,9 @@ def main(argv=None) -> int:
         p = clf.predict_proba(torch.as_tensor(X, dtype=torch.float64, device=a.device))[:, 1]
         for v in p.cpu().tolist():
             print(f"{v:.6f}")
+        if a.explain:
+            ex = _explainer(a)
+            print(format_importance(ex.feature_names, ex.mean_abs(X).cpu().tolist()))
         return 0
     params = OrderedDict(PATIENT_PARAMS)
     for kv in a.set:
@@ -74,6 +109,11 @@ def main(argv=None) -> int:
             return 2
         params[k] = float(v)
     print(format_probability(predict_patient(params, a.model, a.device)))
+    if a.explain:
+        vals = [float(v) for v in params.values()]
+        e = _explainer(a).shap_values([vals])
+        print(format_explanation(e.feature_names, vals, e.phi[0].cpu().tolist(), e.base_value,
+                                 float(e.prediction[0])))
     return 0
 
 

@@ -123,6 +123,12 @@ def stack_infer(x: torch.Tensor, pk) -> torch.Tensor:
     z = (x - pk.mean.to(torch.float64)) * pk.inv_scale.to(torch.float64)
     sv = pk.sv.svt[:F].t().to(torch.float64)
     dec = rbf_decision(z, sv, pk.sv.coef.to(torch.float64), pk.gamma, pk.svc_b)
+    return _stack_tail(x, dec, pk)
+
+
+def _stack_tail(x: torch.Tensor, dec: torch.Tensor, pk) -> torch.Tensor:
+    """Everything of :func:`stack_infer` after the SVC decision values ``dec`` of rows ``x``."""
+    F = pk.F
     p_svc = svc_proba1(dec, pk.probA, pk.probB)
     if pk.stumps is not None:
         st = pk.stumps
@@ -142,3 +148,64 @@ def stack_infer(x: torch.Tensor, pk) -> torch.Tensor:
     p_lg = torch.sigmoid(x @ pk.lr_w.to(torch.float64) + pk.lr_b)
     w0, w1, w2 = pk.meta_w
     return torch.sigmoid(pk.meta_b + w0 * p_svc + w1 * p_gbc + w2 * p_lg)
+
+
+# ----------------------------------------------------------------------------- exact Shapley
+def shapley_weights(F: int) -> torch.Tensor:
+    """``w(s) = s!(F−s−1)!/F!`` for s = 0 … F−1 (f64): the weight of a coalition of size s that
+    a feature joins."""
+    return torch.tensor([math.factorial(s) * math.factorial(F - s - 1) / math.factorial(F)
+                         for s in range(F)], dtype=torch.float64)
+
+
+def coalition_values(x: torch.Tensor, background: torch.Tensor, pk, chunk: int = 16384) -> torch.Tensor:
+    """``v[p, S] = mean_b P(h(S, b))`` with ``h(S, b)[k] = x[p, k]`` if bit k of S is set, else
+    ``background[b, k]`` — every one of the 2^F coalitions, in chunks of ``chunk`` hybrid rows
+    (the RBF kernel matrix of a chunk is all that is ever held).  The rows get
+    :func:`stack_infer`'s arithmetic; only ‖sv − z‖² is formed differently: a hybrid row's
+    distance is a sum of per-feature terms that take one of two values, so the chunk's distances
+    are ``mask @ dxᵀ + (1 − mask) @ dbᵀ`` (two f64 GEMMs) instead of a [chunk, m, F] broadcast."""
+    x = x.to(torch.float64)
+    background = background.to(torch.float64)
+    n, F = x.shape
+    B = background.shape[0]
+    nS = 1 << F
+    k = torch.arange(F)
+    mean, inv = pk.mean.to(torch.float64), pk.inv_scale.to(torch.float64)
+    sv = pk.sv.svt[:F].t().to(torch.float64)
+    coef = pk.sv.coef.to(torch.float64)
+    dx = [((sv - (x[p] - mean) * inv) ** 2).t().contiguous() for p in range(n)]            # [F, m]
+    db = [((sv - (background[b] - mean) * inv) ** 2).t().contiguous() for b in range(B)]
+    v = torch.zeros(n, nS, dtype=torch.float64)
+    for s0 in range(0, nS, chunk):
+        S = torch.arange(s0, min(nS, s0 + chunk))
+        mask = ((S[:, None] >> k[None, :]) & 1).bool()
+        mf = mask.to(torch.float64)
+        for p in range(n):
+            for b in range(B):
+                d2 = mf @ dx[p] + (1.0 - mf) @ db[b]
+                dec = torch.exp(-pk.gamma * d2) @ coef + pk.svc_b
+                v[p, S] += _stack_tail(torch.where(mask, x[p], background[b]), dec, pk)
+    return v / B
+
+
+def shapley_from_values(v: torch.Tensor, F: int) -> torch.Tensor:
+    """``φ[p, k] = Σ_S c_k(S)·v[p, S]``, ``c_k(S) = w(|S|−1)`` if k ∈ S else ``−w(|S|)``."""
+    w = shapley_weights(F)
+    S = torch.arange(1 << F)
+    inS = ((S[:, None] >> torch.arange(F)[None, :]) & 1).bool()         # [2^F, F]
+    size = inS.sum(1)
+    w_in = torch.where(size > 0, w[(size - 1).clamp(min=0)], torch.zeros((), dtype=torch.float64))
+    w_out = torch.where(size < F, w[size.clamp(max=F - 1)], torch.zeros((), dtype=torch.float64))
+    c = torch.where(inS, w_in[:, None], -w_out[:, None])                # [2^F, F]
+    return v.to(torch.float64) @ c
+
+
+def stack_shapley(x: torch.Tensor, background: torch.Tensor, pk, return_values: bool = False):
+    """fp64 mirror of ``ops.stack_shapley``: exact interventional Shapley values of the fused
+    stack's P(class 1) for each row of ``x`` against ``background``.  Returns ``phi [n, F]``,
+    ``base`` (mean background risk, ``v(∅)``), ``pred [n]`` (``v(all)``) and optionally ``v``."""
+    v = coalition_values(x, background, pk)
+    phi = shapley_from_values(v, pk.F)
+    out = (phi, v[0, 0].clone(), v[:, -1].clone())
+    return out + (v,) if return_values else out
