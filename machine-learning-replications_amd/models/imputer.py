@@ -8,6 +8,12 @@ defined distance the column mean of the fit rows is used.  Donor search runs in
 the ``knn_donors`` HIP kernel (tie-break: lowest donor index; sklearn's
 ``argpartition`` tie order is unspecified).  ``n_neighbors > 1`` (uniform mean
 over the k nearest) runs on the host path.
+
+Range of the device search: it runs in f32 on column-centred values, so every centred difference
+``|x − y|`` between a receiver and a donor must stay below ≈ 1.8e19 (``sqrt(FLT_MAX)``).  Past
+that ``(x − y)²`` is +inf in the donor kernels (knn.hip ``knn_donor_kernel``), such a donor never
+passes the strict ``dist < bmax`` test, and a cell whose every candidate overflows gets the column
+mean instead of the f64 donor, without an error.  (Read from the kernel; the suite goes to 1e12.)
 """
 from __future__ import annotations
 
@@ -33,6 +39,17 @@ KNN_DEBUG = __import__("os").environ.get("HFENS_KNN_DEBUG", "0") == "1"
 # of from a host read of the missing-value bitmasks: the donor search launches with no host round trip
 DEVICE_PLAN = __import__("os").environ.get("HFENS_KNN_DEVICE_PLAN", "1") != "0"
 LAST_REFINE: list = []
+# the refine's window-pair list (knn.hip knn_refine) holds max(REFINE_CAP_MIN, REFINE_CAP_PER_ROW · rows)
+# pairs; past it the serial fallback (knn_cand_kernel MODE 1 / 2) evaluates in the scanning threads
+REFINE_CAP_MIN = 1 << 18
+REFINE_CAP_PER_ROW = 16
+
+
+def _refine_debug(work, cap, nr, Mx):
+    """KNN_DEBUG: (rows, re-scanned receivers, window pairs, overflow, pass-1 receivers, ‖m‖) of the
+    knn_refine call that just used ``work`` (synchronising reads)."""
+    o = 4 * cap + 8 * nr * SLOTS + 2 * nr
+    LAST_REFINE.append((nr, int(work[o]), int(work[o + 8]), int(work[o + 9]), int(work[o + 4]), float(Mx[0])))
 
 
 def _masks_u64(miss: torch.Tensor) -> torch.Tensor:
@@ -193,7 +210,7 @@ class KNNImputer(Estimator):
                        Mx.data_ptr(), cnt.data_ptr(), bcnt.data_ptr(), s)
         best = torch.empty(G, n, SLOTS, dtype=i64, device=dev)
         alt = torch.empty(n, SLOTS, dtype=i32, device=dev)
-        cap = max(1 << 18, 16 * n)
+        cap = max(REFINE_CAP_MIN, REFINE_CAP_PER_ROW * n, 1)
         work = torch.empty(4 * cap + n * SLOTS * 8 + 2 * n + 12, dtype=i32, device=dev)
         nd = D32.shape[0]
         mf = None
@@ -216,6 +233,8 @@ class KNNImputer(Estimator):
                          slot[g].data_ptr(), best[g].data_ptr(), alt.data_ptr(), R64.data_ptr(), D64.data_ptr(),
                          Mx.data_ptr(), work.data_ptr(), cap, cnt.data_ptr(), g * SLOTS,
                          mf[0].data_ptr() if mf is not None else 0, mf[1].data_ptr() if mf is not None else 0, s)
+            if KNN_DEBUG:   # (a group past the widest row exits at once: its counters read 0)
+                _refine_debug(work, cap, n, Mx)
         fx = self._fit_X if self._fit_X.is_contiguous() else self._fit_X.contiguous()
         E.knn_apply(Xc.data_ptr(), n, F, rows.data_ptr(), slot.data_ptr(), best.data_ptr(), fx.data_ptr(),
                     self._col_mean.data_ptr(), cnt.data_ptr(), s)
@@ -322,7 +341,7 @@ class KNNImputer(Estimator):
             Mx = Mx.to(torch.float32).contiguous()
             # knn.hip knn_refine scratch: pair keys u64 [cap] | dmin, dwin u64 | didx, didx2 i32 | thr, thr2
             # f32 per slot | pairs [2·cap] | two receiver lists | counts
-            cap = max(1 << 18, 16 * nr)
+            cap = max(REFINE_CAP_MIN, REFINE_CAP_PER_ROW * nr, 1)
             work = torch.empty(4 * cap + nr * SLOTS * 8 + 2 * nr + 12, dtype=torch.int32, device=dev)
         for s0 in range(0, nslot, SLOTS):
             slot = slot_dev[:, s0:s0 + SLOTS].contiguous()
@@ -336,9 +355,7 @@ class KNNImputer(Estimator):
                              slot.data_ptr(), blk.data_ptr(), alt.data_ptr(), R64.data_ptr(), D64.data_ptr(),
                              Mx.data_ptr(), work.data_ptr(), cap, 0, 0, 0, 0, ops.stream_ptr(dev))
                 if KNN_DEBUG:   # re-scanned receivers, window pairs, overflow, pass-1 receivers (synchronising)
-                    o = 4 * cap + 8 * nr * SLOTS + 2 * nr
-                    LAST_REFINE.append((nr, int(work[o]), int(work[o + 8]), int(work[o + 9]), int(work[o + 4]),
-                                        float(Mx[0])))
+                    _refine_debug(work, cap, nr, Mx)
             if nslot != SLOTS:
                 best[:, s0:s0 + SLOTS] = blk
         hmark("imp_knn_launched")

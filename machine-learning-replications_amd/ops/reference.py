@@ -209,3 +209,63 @@ def stack_shapley(x: torch.Tensor, background: torch.Tensor, pk, return_values: 
     phi = shapley_from_values(v, pk.F)
     out = (phi, v[0, 0].clone(), v[:, -1].clone())
     return out + (v,) if return_values else out
+
+
+# ----------------------------------------------------------------------------- KNN imputation
+def knn_impute1(fit, X, undecided_rel: float = 2.0 ** -45):
+    """Brute-force 1-NN imputation (sklearn ``KNNImputer(n_neighbors=1)`` semantics, numpy
+    ``longdouble`` arithmetic; nothing shared with the kernels or ``KNNImputer._impute_host``).
+
+    For a missing cell (r, c) of a column with any fit value the candidates are the fit rows that
+    have c and share at least one present feature with r; the distance is
+    ``F/|common| · Σ_common (x−y)²`` from direct differences; the donor is the lowest index among
+    the exact minima; with no candidate the cell gets the column mean of the fit rows.  Columns
+    with no fit value are dropped.
+
+    Returns ``(out, mean_mask, n_ties, n_undecided)``: the imputed f64 matrix, the mask (shape of
+    ``out``) of the column-mean cells, the number of cells with more than one exact minimum, and
+    the number of cells where a candidate with a DIFFERENT value in column c lies strictly above
+    the minimum by at most ``undecided_rel`` of it — no f64 evaluation can be asked to referee
+    such a cell, so test inputs must have none."""
+    import numpy as np
+    L = np.longdouble
+    fit = np.asarray(fit, dtype=np.float64)
+    X = np.asarray(X, dtype=np.float64)
+    nd, F = fit.shape
+    mf, mx = np.isnan(fit), np.isnan(X)
+    valid = ~mf.all(0)
+    fitL = np.where(mf, 0.0, fit).astype(L)
+    XL = np.where(mx, 0.0, X).astype(L)
+    col_mean = (fitL.sum(0) / np.maximum((~mf).sum(0), 1).astype(L)).astype(np.float64)
+    out = X.copy()
+    mean_mask = np.zeros(X.shape, dtype=bool)
+    n_ties = n_undecided = 0
+    recv = np.nonzero((mx & valid[None, :]).any(1))[0]
+    pf = (~mf).astype(L)
+    step = max(1, (1 << 21) // max(1, nd * F))
+    for s in range(0, recv.size, step):
+        rr = recv[s:s + step]
+        pr = (~mx[rr]).astype(L)
+        both = pr[:, None, :] * pf[None, :, :]
+        diff = XL[rr][:, None, :] - fitL[None, :, :]
+        d2 = (both * diff * diff).sum(-1)
+        common = both.sum(-1)
+        dist = np.where(common > 0, L(F) * d2 / np.maximum(common, 1), L(np.inf))
+        for c in np.nonzero(valid)[0]:
+            j = np.nonzero(mx[rr, c])[0]
+            if j.size == 0:
+                continue
+            donors = np.nonzero(~mf[:, c])[0]
+            dd = dist[np.ix_(j, donors)]
+            dmin = dd.min(1)
+            first = donors[np.argmin(dd, axis=1)]          # first minimum = lowest index
+            none = ~np.isfinite(dmin)
+            vals = fit[first, c]
+            out[rr[j], c] = np.where(none, col_mean[c], vals)
+            mean_mask[rr[j], c] = none
+            ok = ~none
+            n_ties += int(((dd == dmin[:, None]).sum(1)[ok] > 1).sum())
+            near = (dd > dmin[:, None]) & (dd <= dmin[:, None] * (L(1) + L(undecided_rel)))
+            near &= fit[donors, c][None, :] != vals[:, None]
+            n_undecided += int(near.any(1)[ok].sum())
+    return out[:, valid], mean_mask[:, valid], n_ties, n_undecided
