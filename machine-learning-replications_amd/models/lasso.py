@@ -74,12 +74,11 @@ SPECULATIVE_REFIT = os.environ.get("HFENS_LASSO_SPEC_REFIT", "1") != "0"
 # overlap, so nothing the overlap enqueues waits behind the paths.
 SPECULATE = os.environ.get("HFENS_LASSO_SPECULATE", "1") != "0"
 SPEC_ALPHA_INDEX = -1     # the grid point speculated on (tests move it to force a miss)
+# (with the early speculation, the every-alpha refit beside the CV paths is not solved — the hit's
+# refit is the speculative one; a miss solves its one refit after the paths: its 100 one-wave solves
+# ran beside the prelaunched stack and held CUs the GBDT stage kernel and the SMO needed,
+# profiles/r6_runs/r6d: 25.2 vs 19.2 ms / fit with the bases behind the paths)
 EARLY_SPEC = os.environ.get("HFENS_LASSO_EARLY_SPEC", "1") != "0"
-# with the early speculation, the every-alpha refit beside the CV paths is not solved (the hit's refit
-# is the speculative one; a miss solves its one refit after the paths): its 100 one-wave solves ran
-# beside the prelaunched stack and held CUs the GBDT stage kernel and the SMO needed
-# (profiles/r6_runs/r6d: 25.2 vs 19.2 ms / fit with the bases behind the paths)
-EARLY_REFIT_ALL = os.environ.get("HFENS_LASSO_EARLY_REFIT_ALL", "0") == "1"
 
 
 class LassoCV(Estimator):
@@ -118,13 +117,11 @@ class LassoCV(Estimator):
                                              float(self.tol))) for p in range(P)]
         return torch.stack(out).to(Gs.device)
 
-    def fit(self, X, y, group=None, overlap=None, early_overlap=None, tail_out=None):
+    def fit(self, X, y, group=None, overlap=None, early_overlap=None):
         """``overlap``: optional host callable run while the device solves the CV path (between its
         launch and the first read of its result) — host work hidden under the path's GPU time.
         ``early_overlap``: run right after the speculative refit is enqueued, before the alpha grid's
-        host read (only when the speculation runs early, :data:`EARLY_SPEC`).  ``tail_out`` (a list,
-        early speculation only): the fit returns once the CV paths are enqueued and appends the
-        closure that completes it (waits for the paths, picks α, refits) — the caller runs it later."""
+        host read (only when the speculation runs early, :data:`EARLY_SPEC`)."""
         from ..utils.guards import check_finite, finite_flag, raise_flags
         X = as_tensor(X)
         y = as_tensor(y, device=X.device)
@@ -221,9 +218,9 @@ class LassoCV(Estimator):
             for t in (G, q, yy, cnt, grid):
                 t.record_stream(sst)     # (the solve may still read them after fit returns)
         if early:
-            # the CV paths, then every alpha's cold-start refit (below), on ONE side stream: neither
-            # is on the critical path any more (the stacking fit already runs on the speculative
-            # selection), and no further stream changes the measured stream → hardware-queue layout
+            # the CV paths on a side stream: they are not on the critical path any more (the stacking
+            # fit already runs on the speculative selection), and no further stream changes the
+            # measured stream → hardware-queue layout
             from .. import runtime
             pst = runtime.stream(dev, "lasso_refit")
             pst.wait_stream(main)
@@ -233,7 +230,7 @@ class LassoCV(Estimator):
                 path_ev = torch.cuda.Event()
                 path_ev.record(pst)
             coefs.record_stream(main)
-        if dev.type == "cuda" and F <= 64 and SPECULATIVE_REFIT and not (early and not EARLY_REFIT_ALL):
+        if dev.type == "cuda" and F <= 64 and SPECULATIVE_REFIT and not early:
             # the refit at the CV-chosen alpha is a cold-start solve on all rows (sklearn's
             # Lasso(alpha=best).fit); which alpha wins is known only after the CV paths, so solve the
             # cold start for EVERY alpha on a side stream while the CV paths run (one wave each, the
@@ -249,7 +246,6 @@ class LassoCV(Estimator):
                 ev = torch.cuda.Event()
                 ev.record(side)
         dmark("lasso_cv_in")
-        join_ev = None
         if early:
             for t in (G, q, yy, cnt, grid):
                 t.record_stream(pst)
@@ -257,7 +253,6 @@ class LassoCV(Estimator):
                 hmark("lasso_launched")
                 overlap()
                 overlap = None
-            join_ev = path_ev      # (joined in tail(): the MSE below waits for the paths)
         elif spec:
             # the CV paths on a stream of their own: work the overlap enqueues on the caller's stream
             # does not queue behind them (joined before the MSE below, after the overlap)
@@ -279,60 +274,51 @@ class LassoCV(Estimator):
         else:
             coefs = self._solve(G[:k], q[:k], yy[:k], cnt[:k], grid[None].expand(k, -1))   # [k, A, F]
             dmark("lasso_cv_path")
-        def tail():
-            """The CV paths' winner, its refit and the fitted attributes (the host reads)."""
-            nonlocal overlap
-            if join_ev is not None:
-                main.wait_event(join_ev)
-            hmark("lasso_tail")
-            # test MSE per fold and alpha: residual = X_test·w + (ȳ_tr − x̄_tr·w) − y_test
-            inter = my[:k, None] - torch.einsum("pf,paf->pa", mx[:k], coefs)               # [k, A]
-            # Σ_test (x·w + c − y)² from the test-fold moments (all rows minus fold-train rows);
-            # already globally reduced, so no per-row pass and no [k, A, n] intermediate.
-            Txx, Tx, Txy = Sxx[k] - Sxx[:k], sx[k] - sx[:k], Sxy[k] - Sxy[:k]
-            Ty, Tyy, nt = sy[k] - sy[:k], Syy[k] - Syy[:k], cnt[k] - cnt[:k]
-            c = inter
-            se = (torch.einsum("paf,pfg,pag->pa", coefs, Txx, coefs)
-                  + 2 * c * torch.einsum("pf,paf->pa", Tx, coefs) - 2 * torch.einsum("pf,paf->pa", Txy, coefs)
-                  + nt[:, None] * c * c - 2 * c * Ty[:, None] + Tyy[:, None])
-            mse = se / nt[:, None]                                                          # [k, A]
-            mean_mse = mse.mean(0)
-            best_dev = torch.argmin(mean_mse)
-            self.coef_dev_ = None
-            if refit_all is not None:
-                # the winner's coefficients stay on the device (no host read): a caller's overlap can
-                # queue work that depends on them (SelectFromModel's device column list → the stacking
-                # trainer's SVC batch) before this fit reads anything back
-                torch.cuda.current_stream(dev).wait_event(ev)
-                self.coef_dev_ = refit_all.index_select(0, best_dev.reshape(1))[0, 0]
-            if overlap is not None:
-                overlap()
-            best = int(best_dev)
-            hmark("lasso_best_read")
-            self.alpha_ = float(grid[best])
-            self.alphas_ = grid
-            self.mse_path_ = mse.t()
-            if refit_all is not None:
-                w = refit_all[best, 0]
-            elif (early and best == SPEC_ALPHA_INDEX % A
-                  and float(self.spec_alpha_dev_) == float(grid[best])):
-                # the speculation hit: its refit IS the refit at the chosen alpha (same kernel, same
-                # inputs, the same alpha bits)
-                w = self.coef_spec_dev_
-            else:
-                final = self._solve(G[k:], q[k:], yy[k:], cnt[k:], grid[best:best + 1][None])
-                w = final[0, 0]
-            self.coef_ = w
-            self.intercept_ = my[k] - mx[k] @ w
-            self.n_features_in_ = F
-            return self
-
-        if tail_out is not None and early:
-            # the caller completes the fit later (pipeline.develop: after finishing the stacking fit
-            # enqueued on the speculative selection, so the host waits for both at once)
-            tail_out.append(tail)
-            return self
-        return tail()
+        # the CV paths' winner, its refit and the fitted attributes (the host reads)
+        if early:
+            main.wait_event(path_ev)
+        hmark("lasso_tail")
+        # test MSE per fold and alpha: residual = X_test·w + (ȳ_tr − x̄_tr·w) − y_test
+        inter = my[:k, None] - torch.einsum("pf,paf->pa", mx[:k], coefs)               # [k, A]
+        # Σ_test (x·w + c − y)² from the test-fold moments (all rows minus fold-train rows);
+        # already globally reduced, so no per-row pass and no [k, A, n] intermediate.
+        Txx, Tx, Txy = Sxx[k] - Sxx[:k], sx[k] - sx[:k], Sxy[k] - Sxy[:k]
+        Ty, Tyy, nt = sy[k] - sy[:k], Syy[k] - Syy[:k], cnt[k] - cnt[:k]
+        c = inter
+        se = (torch.einsum("paf,pfg,pag->pa", coefs, Txx, coefs)
+              + 2 * c * torch.einsum("pf,paf->pa", Tx, coefs) - 2 * torch.einsum("pf,paf->pa", Txy, coefs)
+              + nt[:, None] * c * c - 2 * c * Ty[:, None] + Tyy[:, None])
+        mse = se / nt[:, None]                                                          # [k, A]
+        mean_mse = mse.mean(0)
+        best_dev = torch.argmin(mean_mse)
+        self.coef_dev_ = None
+        if refit_all is not None:
+            # the winner's coefficients stay on the device (no host read): a caller's overlap can
+            # queue work that depends on them (SelectFromModel's device column list → the stacking
+            # trainer's SVC batch) before this fit reads anything back
+            torch.cuda.current_stream(dev).wait_event(ev)
+            self.coef_dev_ = refit_all.index_select(0, best_dev.reshape(1))[0, 0]
+        if overlap is not None:
+            overlap()
+        best = int(best_dev)
+        hmark("lasso_best_read")
+        self.alpha_ = float(grid[best])
+        self.alphas_ = grid
+        self.mse_path_ = mse.t()
+        if refit_all is not None:
+            w = refit_all[best, 0]
+        elif (early and best == SPEC_ALPHA_INDEX % A
+              and float(self.spec_alpha_dev_) == float(grid[best])):
+            # the speculation hit: its refit IS the refit at the chosen alpha (same kernel, same
+            # inputs, the same alpha bits)
+            w = self.coef_spec_dev_
+        else:
+            final = self._solve(G[k:], q[k:], yy[k:], cnt[k:], grid[best:best + 1][None])
+            w = final[0, 0]
+        self.coef_ = w
+        self.intercept_ = my[k] - mx[k] @ w
+        self.n_features_in_ = F
+        return self
 
 
 class SelectFromModel(Estimator):
@@ -356,14 +342,12 @@ class SelectFromModel(Estimator):
         key = torch.where(rank < k, idx, idx + F)
         return torch.sort(key, stable=True).values[:k]
 
-    def fit(self, X, y, group=None, overlap=None, early_overlap=None, tail_out=None):
+    def fit(self, X, y, group=None, overlap=None, early_overlap=None):
         """``overlap`` / ``early_overlap``: host callables run under the LassoCV path (see
         :meth:`LassoCV.fit`).  With threshold=-inf and max_features, ``cols_dev_`` (the selected
         columns on the device, from the speculative refit when there is one) is set before either
         runs; ``early_overlap`` runs as soon as the speculative selection is enqueued (before the
-        LassoCV's host read) or, without an early speculation, right before ``overlap``.
-        ``tail_out``: see :meth:`LassoCV.fit` — the selection is then completed by the appended
-        closure."""
+        LassoCV's host read) or, without an early speculation, right before ``overlap``."""
         self.cols_dev_ = None
         self.cols_host_ = None
         if (overlap is not None or early_overlap is not None) and isinstance(self.estimator, LassoCV):
@@ -407,15 +391,7 @@ class SelectFromModel(Estimator):
                 early()
                 if user_late is not None:
                     user_late()
-            inner = [] if tail_out is not None else None
-            self.estimator_ = self.estimator.fit(X, y, group=group, overlap=late, early_overlap=early,
-                                                 tail_out=inner)
-            if inner:
-                def tail():
-                    inner[0]()
-                    self._select()
-                tail_out.append(tail)
-                return self
+            self.estimator_ = self.estimator.fit(X, y, group=group, overlap=late, early_overlap=early)
         else:
             self.estimator_ = self.estimator.fit(X, y, group=group)
             for f in (early_overlap, overlap):

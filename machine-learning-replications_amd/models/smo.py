@@ -740,10 +740,6 @@ WS_GRAPH_CHUNK = int(os.environ.get("HFENS_SVM_WS_GRAPH_CHUNK", "32"))   # round
 _WS_GRAPHS: dict = {}
 WS_BIG_CHUNK = int(os.environ.get("HFENS_SVM_WS_BIG_CHUNK", "64"))
 WS_THREADS = int(os.environ.get("HFENS_SVM_WS_THREADS", "256"))      # inner-solver workgroup (256 or 512)
-WS_G0_FIRST = os.environ.get("HFENS_SVM_WS_G0_FIRST", "1") == "1"
-# the last (smallest-problem) group on a side stream of its own (runtime FIT_STREAMS svc_ws_2, normal
-# priority) instead of the caller's high-priority stream
-WS_LAST_SIDE = os.environ.get("HFENS_SVM_WS_LAST_SIDE", "0") == "1"
 _WS_SYNC = [False]   # set while re-solving a batch that did not converge within WS_ROUNDS_AHEAD
 
 
@@ -776,7 +772,7 @@ def _ws_groups(live, device) -> List[List[int]]:
 
 
 def _solve_ws(E, live, zcat, zoffs, aoffs, F, device, eps, max_iter_cap, s, steps_per_check=None,
-              seed=None, q=None, groups=None, deps_out=None, after_first=None):
+              seed=None, q=None, groups=None, after_first=None):
     """``seed``: a feasible α (per point, this batch's layout) to start from instead of α = 0
     (:func:`_cascade_seed`) — every value AT a bound or at least f32 resolution inside it (the
     selection keys read f64 α, the inner solve f32 α: a value within an f32 ulp of a bound is free
@@ -832,11 +828,11 @@ def _solve_ws(E, live, zcat, zoffs, aoffs, F, device, eps, max_iter_cap, s, step
     done = [0] * len(groups)
     # the first group (the largest problems: the batch's critical path) gets its first rounds
     # enqueued as soon as its own state is, before the other groups' states are built
-    g0_first = WS_G0_FIRST and not sync and not use_graph and len(groups) > 1
+    g0_first = not sync and not use_graph and len(groups) > 1
     for gi, idx in enumerate(groups):
         # the last (smallest) group on the caller's stream, the others on process-lifetime side streams
         side = None
-        if gi == len(groups) - 1 and not (WS_LAST_SIDE and cuda and gi > 0):
+        if gi == len(groups) - 1:
             st = s
         else:
             from .. import runtime
@@ -899,17 +895,9 @@ def _solve_ws(E, live, zcat, zoffs, aoffs, F, device, eps, max_iter_cap, s, step
     if evs is not None:
         LAST_WS_EVENTS.clear()
         LAST_WS_EVENTS.update(evs, chunk=chunk if not sync else None)
-    # split join (deps_out given, no graphs): the caller's stream does NOT wait for every group —
-    # the consumers wait for the groups of the problems they read (deps_out["wait"]); everything
-    # that needs the whole batch (ρ / iterations of every problem, the error word) is assembled on
-    # the first group's stream after it has waited for the others (deps_out["join"]).  The stacking
-    # fit's Platt / out-of-fold / meta chain reads only the Platt-CV and fold problems, so it no
-    # longer waits for the refit's final problem — the longest one (profiles/r6_headline.md).
-    split = deps_out is not None and not use_graph and len(runs) > 1 and cuda
     for r in runs:
         if r["side"] is not None:
-            if not split:
-                caller.wait_stream(r["side"])
+            caller.wait_stream(r["side"])
             for t in (alpha, G, zn, keys, zcat, r["rho"], r["iters"], r["idx_dev"]) + ((seed,) if seed is not None else ()):
                 t.record_stream(r["side"])
     if use_graph:
@@ -918,47 +906,6 @@ def _solve_ws(E, live, zcat, zoffs, aoffs, F, device, eps, max_iter_cap, s, step
         alpha = alpha.clone()
     if len(runs) == 1:
         rho, iters, err = runs[0]["rho"], runs[0]["iters"], runs[0]["err"]
-    elif split:
-        ev_of = []
-        for r in runs:
-            ev = torch.cuda.Event()
-            ev.record(r["side"] if r["side"] is not None else caller)
-            ev_of.append(ev)
-        J = runs[0]["side"] if runs[0]["side"] is not None else caller
-        for gi, ev in enumerate(ev_of):
-            if runs[gi]["side"] is not J:
-                J.wait_event(ev)
-        with torch.cuda.stream(J):
-            rho = torch.empty(P, dtype=torch.float64, device=device)
-            iters = torch.empty(P, dtype=torch.int32, device=device)
-            for r in runs:
-                rho.index_copy_(0, r["idx_dev"], r["rho"])
-                iters.index_copy_(0, r["idx_dev"], r["iters"])
-            err = torch.stack([r["err"] for r in runs]).amax().reshape(1)
-            join_ev = torch.cuda.Event()
-            join_ev.record(J)
-        for t in (rho, iters, err):
-            t.record_stream(caller)
-        run_of = np.empty(P, dtype=np.int64)
-        for gi, r in enumerate(runs):
-            run_of[r["idx"]] = gi
-
-        def wait(stream, problems):
-            """Make ``stream`` wait for the groups holding ``problems`` (indices into live)."""
-            for gi in sorted({int(run_of[k]) for k in problems}):
-                stream.wait_event(ev_of[gi])
-
-        def rho_for(stream, problems):
-            """ρ of every problem [P] on ``stream``, valid for the groups holding ``problems``."""
-            gis = sorted({int(run_of[k]) for k in problems})
-            with torch.cuda.stream(stream):
-                rr = torch.zeros(P, dtype=torch.float64, device=device)
-                for gi in gis:
-                    stream.wait_event(ev_of[gi])
-                    runs[gi]["rho"].record_stream(stream)
-                    rr.index_copy_(0, runs[gi]["idx_dev"], runs[gi]["rho"])
-            return rr
-        deps_out.update(wait=wait, rho_for=rho_for, join=J, join_ev=join_ev)
     else:
         rho = torch.empty(P, dtype=torch.float64, device=device)
         iters = torch.empty(P, dtype=torch.int32, device=device)
@@ -1366,7 +1313,7 @@ def _solve_device(probs: List[_Prob], Zs, device, eps, max_iter_cap=None, group=
     solver = _pick_solver(max_l, F)
     solve = _solve_ws if solver == "ws" else _solve_exact
     # ---- label-only tables of the post-SMO launches, uploaded while the main rounds run — once
-    # every group's first rounds are enqueued (TABLES_AFTER_FIRST; each in-stream upload queued
+    # every working-set group's first rounds are enqueued (each in-stream upload queued
     # behind the whole SMO cost ≈ 30 µs on the critical path; ahead of the parts they delayed the
     # parts' enqueue, ahead of the main rounds the critical group's first round):
     # the signs of y·α, the Platt decision table (+ the stacking fit's out-of-fold rows,
@@ -1387,7 +1334,7 @@ def _solve_device(probs: List[_Prob], Zs, device, eps, max_iter_cap=None, group=
             oof = []
             # (``oof_items`` may be a callable: the caller's out-of-fold rows formed only now)
             oi = oof_items() if callable(oof_items) else oof_items
-            if oi and not (SPLIT_JOIN and group is None):
+            if oi:
                 finals = {p.fit: k for k, p in enumerate(live) if p.fold < 0}
                 oof = [(finals[f], Zt) for f, Zt in oi if f in finals]
                 if len(oof) != len(oi):
@@ -1422,7 +1369,6 @@ def _solve_device(probs: List[_Prob], Zs, device, eps, max_iter_cap=None, group=
                            rowk=rowk_d)
         tabs.update(sign_d=sign_d, pre_dec=pre_dec)
         hmark("svc_tables")
-    deps: dict = {}
     if group is None:
         kw = {}
         if solver == "ws" and CASCADE and (CASCADE_KC or not ws_kc(F, max_l)):
@@ -1430,9 +1376,7 @@ def _solve_device(probs: List[_Prob], Zs, device, eps, max_iter_cap=None, group=
             if seed is not None:
                 kw["seed"] = seed
                 hmark("svc_cascade_seeded")
-        if solver == "ws" and SPLIT_JOIN:
-            kw["deps_out"] = deps
-        if solver == "ws" and TABLES_AFTER_FIRST:
+        if solver == "ws":
             # (built while the device runs the first rounds, off the critical group's enqueue)
             kw["after_first"] = prep_tables
         else:
@@ -1453,9 +1397,6 @@ def _solve_device(probs: List[_Prob], Zs, device, eps, max_iter_cap=None, group=
         prep_tables()
         alpha, rho, iters, err = _solve_distributed(solve_local, live, aoffs[-1], aoffs, device, group)
     out["smo_err"] = err
-    J = deps.get("join")
-    if J is not None:
-        out["_deps"] = deps     # (consumers wait for the groups they read; finish joins them all)
     for k, p in enumerate(live):
         a0 = aoffs_start[k]
         out[id(p)] = (alpha[a0:a0 + p.l], rho[k], iters[k])
@@ -1466,29 +1407,20 @@ def _solve_device(probs: List[_Prob], Zs, device, eps, max_iter_cap=None, group=
     if EARLY_READ and fin and len({f for f, _ in fin}) == len(fin):
         f64 = torch.float64
         ks = [k for _, k in fin]
-        # (split join: on the joining stream, behind every group)
-        with (torch.cuda.stream(J) if J is not None else contextlib.nullcontext()):
-            kidx = _to_dev(np.array(ks, dtype=np.int64), device)
-            parts = ([(alpha[aoffs_start[k]:aoffs_start[k] + live[k].l] > 0).to(f64) for k in ks]
-                     + [rho.index_select(0, kidx).to(f64).reshape(-1), iters.index_select(0, kidx).to(f64).reshape(-1)]
-                     + ([err.to(f64).reshape(-1).abs().max().reshape(1)] if err is not None else []))
-            early_dev = torch.cat(parts)
-            early_host, ev = stage(early_dev)     # (finite once landed: polled by finish_svc_batch)
+        kidx = _to_dev(np.array(ks, dtype=np.int64), device)
+        parts = ([(alpha[aoffs_start[k]:aoffs_start[k] + live[k].l] > 0).to(f64) for k in ks]
+                 + [rho.index_select(0, kidx).to(f64).reshape(-1), iters.index_select(0, kidx).to(f64).reshape(-1)]
+                 + ([err.to(f64).reshape(-1).abs().max().reshape(1)] if err is not None else []))
+        early_dev = torch.cat(parts)
+        early_host, ev = stage(early_dev)     # (finite once landed: polled by finish_svc_batch)
         out["_early"] = dict(host=early_host, ev=ev, ids=[id(live[k]) for k in ks], has_err=err is not None,
                              keep=early_dev)
     # y·α of every problem in f32 (the decision kernels' coefficients), kept with the problems' rows
     # for the held-out decisions below and the stacking trainer's device OOF (enqueue_svc_oof)
     # (the signs built on the host and uploaded in one copy, before the rounds)
     sign_d, pre_dec = tabs["sign_d"], tabs["pre_dec"]
-    rho_pl = rho
-    if J is not None:
-        # the Platt decisions read only the Platt-CV problems: wait for their groups alone
-        cur = torch.cuda.current_stream(device)
-        deps["wait"](cur, [k for k, _ in platt])
-        rho_pl = deps["rho_for"](cur, [k for k, _ in platt])
     coef = (sign_d * alpha.to(torch.float32)).contiguous()
-    out["_dec"] = dict(zcat=zcat, coef=coef, F=F, zoff={id(p): zoffs[k] for k, p in enumerate(live)},
-                       sign=sign_d, alpha=alpha, kof={id(p): k for k, p in enumerate(live)})
+    out["_dec"] = dict(zcat=zcat, coef=coef, F=F, zoff={id(p): zoffs[k] for k, p in enumerate(live)})
     # ---- Platt held-out decision values of every CV sub-model: one batched launch — with the
     # stacking fit's out-of-fold rows (``oof_items``: [(fit f, fold-f-scaled rows)], decided by fit f's
     # final problem) in the SAME launch, so enqueue_svc_oof needs no decision launch of its own
@@ -1506,7 +1438,7 @@ def _solve_device(probs: List[_Prob], Zs, device, eps, max_iter_cap=None, group=
         # the decision values are assembled inside the Platt kernel from these partials (row r of
         # part: problem rowk[r]'s held-out point, d = −(Σ part[r] − ρ))
         out["platt_src"] = dict(part=pdd["part"], S=pdd["S"], rowk=pdd["rowk"],
-                                rho=rho_pl.to(torch.float64).contiguous(), keep=(pdd["hcat"], pdd["ddev"], zsv, csv, cnt))
+                                rho=rho.to(torch.float64).contiguous(), keep=(pdd["hcat"], pdd["ddev"], zsv, csv, cnt))
     return out
 
 
@@ -1559,15 +1491,6 @@ EXACT_MAX_POINTS = int(os.environ.get("HFENS_SVM_EXACT_MAX", "150000"))
 # kernels), so finish_svc_batch's support extraction overlaps them (same-box A/B of the headline:
 # within its ±0.7 ms run-to-run spread, scripts/probes/gpu_r4an.sh, profiles/r4_runs/early_read_ab.log)
 EARLY_READ = os.environ.get("HFENS_SVC_EARLY_READ", "1") != "0"
-# split join of the working-set groups (_solve_ws deps_out): the Platt decisions and the stacking
-# fit's out-of-fold column wait only for the groups of the problems they read, not for the refit's
-# final problem (the longest, whose model is only needed at the end)
-# (measured, profiles/r6_runs/r6r: no gain on the headline — the Platt-CV groups end within
-# ≈ 0.1 ms of the refit's 10k problem — so it is off by default: 18.07 / 17.79 vs 17.92 / 18.11 ms)
-SPLIT_JOIN = os.environ.get("HFENS_SVM_SPLIT_JOIN", "0") == "1"
-# the post-SMO label-only tables built once every working-set group's first rounds are enqueued
-# ("0": before the main rounds, behind the cascade parts)
-TABLES_AFTER_FIRST = os.environ.get("HFENS_SVC_TABLES_AFTER_FIRST", "1") == "1"
 EXACT_HOST_MAX = int(os.environ.get("HFENS_SVM_EXACT_HOST_MAX", "32768"))
 GRAM_BUDGET = float(os.environ.get("HFENS_SVM_GRAM_BUDGET", str(96 << 30)))
 
@@ -1868,29 +1791,19 @@ def enqueue_svc_oof(st: dict, items, meta: torch.Tensor, col: int) -> bool:
     if pre is not None and pre["ids"] == [(f, id(Zt)) for f, Zt, _ in items] and pre["hoff"] == hoff:
         # the decisions came with the Platt launch (launch_svc_batch oof_items): only the sigmoid
         dec = pre["part"][pre["hoff0"]:pre["hoff0"] + hoff].to(torch.float64).sum(1).contiguous()
-        return _svc_oof_tail(st, items, finals, dec, hs, meta, col, device, None, (pre,))
+        return _svc_oof_tail(st, items, finals, dec, hs, meta, col, device, (pre,))
     hcat = torch.cat([Zt.to(torch.float32) for _, Zt, _ in items]).contiguous()
     part = torch.zeros(hoff, S, dtype=torch.float32, device=device)
     ddev = _dev_struct(dt, device)
     if st.get("gamma_dev") is not None:
         st["gamma_dev"].patch(ddev, _DEC_DT, "ngl2e", [f for f, _, _ in items])
-    deps = sol.get("_deps")
-    coef, rho_src = dec_state["coef"], None
-    if deps is not None:
-        # split join: wait for the groups of these final problems only, then y·α and ρ from them
-        cur = torch.cuda.current_stream(device)
-        ks = [dec_state["kof"][id(p)] for p in finals]
-        deps["wait"](cur, ks)
-        coef = (dec_state["sign"] * dec_state["alpha"].to(torch.float32)).contiguous()
-        rho_src = deps["rho_for"](cur, ks)
+    coef = dec_state["coef"]
     zsv, csv, cnt = _sv_compact(E, dec_state["zcat"], coef, dec_state["F"], ddev, len(items), device, s)
     E.svm_dec_batch(zsv.data_ptr(), csv.data_ptr(), hcat.data_ptr(), dec_state["F"],
                     ddev.data_ptr(), len(items), int(max(hs)), S, part.data_ptr(),
                     cnt.data_ptr() if cnt is not None else 0, s)
     dec = part.to(torch.float64).sum(1).contiguous()
-    return _svc_oof_tail(st, items, finals, dec, hs, meta, col, device,
-                         rho_src.index_select(0, _to_dev(np.asarray(ks, dtype=np.int64), device)).contiguous()
-                         if rho_src is not None else None, (hcat, part, ddev, coef, zsv, csv, cnt))
+    return _svc_oof_tail(st, items, finals, dec, hs, meta, col, device, (hcat, part, ddev, coef, zsv, csv, cnt))
 
 
 # the decision launches read only each problem's support vectors (svm_sv_compact: ≈ 45 % of the
@@ -1899,9 +1812,6 @@ def enqueue_svc_oof(st: dict, items, meta: torch.Tensor, col: int) -> bool:
 DEC_COMPACT = os.environ.get("HFENS_SVC_DEC_COMPACT", "1") != "0"
 # the Platt sigmoid fits with each fit's points over 8 workgroups (svm.hip platt_coop_kernel)
 PLATT_COOP = os.environ.get("HFENS_PLATT_COOP", "1") != "0"
-# finish_svc_batch: the final models' set_fitted before the Platt pairs are read back (their
-# bookkeeping overlaps the decision / Platt kernels; SVC.set_platt installs the pair after)
-SET_BEFORE_PLATT = os.environ.get("HFENS_SVC_SET_BEFORE_PLATT", "1") != "0"
 
 
 def _sv_compact(E, zcat, coef, F, ddev, P, device, s):
@@ -1917,7 +1827,7 @@ def _sv_compact(E, zcat, coef, F, ddev, P, device, s):
     return zc, cc, cnt
 
 
-def _svc_oof_tail(st, items, finals, dec, hs, meta, col, device, rho, keep) -> bool:
+def _svc_oof_tail(st, items, finals, dec, hs, meta, col, device, keep) -> bool:
     """The out-of-fold probabilities from the decision values ``dec`` (rows of ``items`` in order):
     Platt sigmoid + coupling with each final model's ρ and (A, B), scattered into ``meta[:, col]``."""
     from .. import ops
@@ -1928,8 +1838,7 @@ def _svc_oof_tail(st, items, finals, dec, hs, meta, col, device, rho, keep) -> b
     model = torch.repeat_interleave(torch.arange(len(items), dtype=torch.int32),
                                     torch.as_tensor(hs, dtype=torch.int64))
     model = _to_dev(model.numpy(), device)
-    if rho is None:
-        rho = torch.stack([st["sol"][id(p)][1].reshape(()).to(torch.float64) for p in finals]).contiguous()
+    rho = torch.stack([st["sol"][id(p)][1].reshape(()).to(torch.float64) for p in finals]).contiguous()
     sel = _to_dev(np.array([pl.index(f) for f, _, _ in items], dtype=np.int64), device)
     AB = st["ABt"].view(-1, 2).index_select(0, sel).reshape(-1).contiguous()
     rows = torch.cat([r.to(torch.int64) for _, _, r in items]).contiguous()
@@ -1951,9 +1860,6 @@ def finish_svc_batch(st: dict, defer=None):
         return st["svcs"]
     svcs, Zs, meta, all_probs, sol, AB, device = (st["svcs"], st["Zs"], st["meta"], st["all_probs"],
                                                    st["sol"], st["AB"], st["device"])
-    if sol.get("_deps") is not None:
-        # (split join) everything from here on sees the whole batch: the refit's final problem too
-        torch.cuda.current_stream(device).wait_event(sol["_deps"]["join_ev"])
     early = sol.get("_early")
     finals = [[q for q in all_probs if q.fit == f and q.fold < 0][0] for f in range(len(svcs))]
     if early is not None and early["ids"] != [id(p) for p in finals]:
@@ -2053,10 +1959,10 @@ def finish_svc_batch(st: dict, defer=None):
     later = [f for f in range(len(svcs)) if defer is not None and f in defer]
     now = [f for f in range(len(svcs)) if f not in later]
     kws = {f: prep_one(f) for f in now}     # (with the early read: while the Platt kernels run)
-    pre = SET_BEFORE_PLATT and early is not None and st.get("ab_host") is not None and st["ABt"] is not None
+    pre = early is not None and st.get("ab_host") is not None and st["ABt"] is not None
     if pre:
-        # set_fitted too while the Platt kernels run; the pair (device: the kernel's own output)
-        # goes in after its read-back
+        # set_fitted too while the Platt kernels run (the bookkeeping overlaps the decision / Platt
+        # kernels); the pair (device: the kernel's own output) goes in after its read-back
         for f in now:
             set_one(f, kws[f], platt=False)
     read_ab()

@@ -56,13 +56,9 @@ SKIP_FOLD_SVC = os.environ.get("HFENS_SKIP_FOLD_SVC", "1") != "0"
 # their out-of-fold columns come from the device node tables / coefficients (ops/csrc/stackdev.hip),
 # and only the refit models are finished.  0 = the synchronous per-batch fits of round 4.
 DEVICE_BASES = os.environ.get("HFENS_DEVICE_BASES", "1") != "0"
-# the meta model's launch enqueued before the SVC's results are read back (0: after them)
+# the meta model's launch enqueued before the SVC's results are read back (0: after them), with its
+# set_fitted done at that launch (the fit's tail then only reads its error word / guards)
 EARLY_META = os.environ.get("HFENS_EARLY_META", "1") != "0"
-# ... with its set_fitted done at that launch (the fit's tail then only reads its error word / guards)
-META_PRESET = os.environ.get("HFENS_META_PRESET", "1") != "0"
-# the GBC / L1-LR guards resolved BEFORE the SVC's read-back when their staged copy has already
-# landed (they finish milliseconds before the SMO): off the tail's host path
-BASES_EARLY_RESOLVE = os.environ.get("HFENS_BASES_EARLY_RESOLVE", "1") != "0"
 
 
 def _kind(est):
@@ -245,8 +241,11 @@ def plan_stacking_start(clf, y_np: np.ndarray):
     out = np.empty(nf1 * 7 * n, dtype=np.int64)
     meta = np.empty(nf1 * 21, dtype=np.int64)
     E = ops.ext()
+    # (keep: the native routine gets raw pointers — the job holds the arrays until it has run, so a
+    # caller that never joins does not free them under it)
     done = _plan_worker().submit(E.stack_plan_host, y_np.ctypes.data, n, N_FOLDS, seed, folds.ctypes.data,
-                                 rows.ctypes.data, lens.ctypes.data, out.ctypes.data, meta.ctypes.data)
+                                 rows.ctypes.data, lens.ctypes.data, out.ctypes.data, meta.ctypes.data,
+                                 keep=(y_np, folds, rows, lens, out, meta))
     balanced = svc.class_weight == "balanced"
 
     def join():
@@ -272,10 +271,11 @@ def plan_stacking_start(clf, y_np: np.ndarray):
 class _Done:
     """Completion of one :class:`_PlanWorker` job."""
 
-    def __init__(self):
+    def __init__(self, keep=()):
         import threading
         self._ev = threading.Event()
         self.error = None
+        self.keep = keep      # arrays the job reads / writes through raw pointers, held until it has run
 
     def wait(self):
         self._ev.wait()
@@ -300,9 +300,11 @@ class _PlanWorker:
             except BaseException as e:   # re-raised by the joining thread
                 done.error = e
             done._ev.set()
+            done.keep = ()
 
-    def submit(self, fn, *args) -> _Done:
-        done = _Done()
+    def submit(self, fn, *args, keep=()) -> _Done:
+        """``keep``: the objects behind the raw pointers in ``args`` — alive until ``fn`` returns."""
+        done = _Done(keep)
         self._q.put((fn, args, done))
         return done
 
@@ -408,7 +410,7 @@ def _launch_bases(stc):
             # meta model waits for both, and the LR behind the GBC ended last (r6i: lg_done 17.9 vs
             # the SVC's out-of-fold column at 17.5 ms)
             order = [i for i in range(len(clf.estimators)) if i not in svc_cols]
-            if LR_FIRST and dev_bases is not None:
+            if dev_bases is not None:
                 for i in order:
                     if _kind(clf.estimators[i][1]) == "gbc":
                         dev_bases["prebin"](clf.estimators[i][1])
@@ -464,9 +466,11 @@ def _finish_concurrent(stc):
         from ..parallel.stack import finish_svc_batch_distributed
     with stc["timer"].stage("fit_bases(svc || gbc+lr)"):
         resolved = False
-        if dev_bases is not None and BASES_EARLY_RESOLVE and dev_bases["deferred"].ready():
-            # (their kernels have finished: the read is a look at host memory.  A fallback hook
-            # re-solves on the caller's stream, after the bases' own)
+        if dev_bases is not None and dev_bases["deferred"].ready():
+            # (the GBC / L1-LR guards before the SVC's read-back when their staged copy has already
+            # landed — they finish milliseconds before the SMO — off the tail's host path: the read
+            # is a look at host memory.  A fallback hook re-solves on the caller's stream, after
+            # the bases' own)
             main.wait_stream(other)
             dev_bases["deferred"].resolve()
             resolved = True
@@ -505,18 +509,11 @@ PRELAUNCH_SVC = os.environ.get("HFENS_PRELAUNCH_SVC", "1") != "0"
 # only the SVC batch) on the speculative selection: the bases' chain (≈ 7 ms from the selection) ran
 # after lasso_fit before and ended beside the SMO (profiles/r6_runs/r6a: lg_done 18.1 vs svc_oof 18.5 ms).
 # The bases go in right behind the SVC batch (prelaunch_bases from the early overlap; after the CV
-# paths with pipeline.BASES_AFTER_CV — measured slower, profiles/r6_runs/r6e)
+# paths they were measured slower, profiles/r6_runs/r6e)
 PRELAUNCH_BASES = os.environ.get("HFENS_PRELAUNCH_BASES", "1") != "0"
 # device γ for the stacking fit's SVC batch whenever eligible (working-set solver, planned labels,
 # gamma='scale'): no host read of the scaled rows' variance before the SMO, prelaunched or not
 GAMMA_DEV = os.environ.get("HFENS_SVC_GAMMA_DEV", "1") != "0"
-# the GBC / LR / meta device state (index uploads, label prep) built before the SVC batch is enqueued
-# ("before") or after it on the bases stream ("after", default: the SVC batch's host enqueue starts
-# ≈ 0.4 ms earlier; same fit time on one box, 18.99 / 18.19 vs 19.03 / 18.23 ms, profiles/r6_runs/r6i);
-# built after it on the CALLER's stream it made the GBC's host bin fit wait for the whole SMO
-# (profiles/r6_runs/r6h: gbc_binned 16.7 ms)
-BASES_SETUP = os.environ.get("HFENS_BASES_SETUP", "after")
-LR_FIRST = os.environ.get("HFENS_LR_FIRST", "1") != "0"
 # the SVC's out-of-fold decisions computed in the batch's Platt decision launch (one launch, the same
 # partials bit for bit: extra all-zero split columns add exact zeros)
 MERGED_OOF_DEC = os.environ.get("HFENS_MERGED_OOF_DEC", "1") != "0"
@@ -569,8 +566,8 @@ def prelaunch_stack(clf, X_full: torch.Tensor, cols_dev: torch.Tensor, y: torch.
 
 def prelaunch_bases(pre) -> None:
     """The GBC / L1-LR batches and the meta model of a :func:`prelaunch_stack` state, enqueued (the
-    pipeline calls it under the LassoCV path right after the CV paths are launched: the SVC batch
-    first, the LassoCV's own paths second, the bases last — each waits on the host before it)."""
+    pipeline calls it from the LassoCV's early overlap, right behind the SVC batch and before the
+    LassoCV's own CV paths are launched)."""
     stc = pre["state"] if pre is not None else None
     if stc is not None and PRELAUNCH_BASES and stc["concurrent"] and not stc["bases_done"]:
         _launch_bases(stc)
@@ -657,17 +654,19 @@ def launch_stacking(clf, X: torch.Tensor, y: torch.Tensor, timer: StageTimer = N
             # out-of-fold columns only the features' guard and the intercept column remain
             from .logreg_solver import logreg_label_prep
             lprep = logreg_label_prep(fm, y64, n, dev) if X.is_cuda else None
-            early = {"launch": lambda: launch_logreg_batch(fm, meta, y64, prep=lprep, preset=META_PRESET)}
+            early = {"launch": lambda: launch_logreg_batch(fm, meta, y64, prep=lprep, preset=True)}
         dev_bases = None
         if group is None and X.is_cuda and DEVICE_BASES:
-            dev_bases = _device_bases(clf, X, y, masks, folds_np, meta, plan, early, oof)
+            dev_bases = _device_bases(clf, X, y, masks, folds_np, meta, early, oof)
         stc.update(early=early, dev_bases=dev_bases)
-    if BASES_SETUP == "before" or not X.is_cuda:
+    if not X.is_cuda:
         bases_state()
         stc["concurrent"] = _launch_svc(stc)
     else:
-        # the SVC batch first (the fit's critical path); the other bases' device state after it, on
-        # the bases stream
+        # the SVC batch first (the fit's critical path: its host enqueue starts ≈ 0.4 ms earlier);
+        # the other bases' device state (index uploads, label prep) after it, on the bases stream —
+        # on the CALLER's stream it made the GBC's host bin fit wait for the whole SMO
+        # (profiles/r6_runs/r6h: gbc_binned 16.7 ms)
         stc["concurrent"] = _launch_svc(stc)
         from .. import runtime
         other = runtime.stream(dev, "bases")
@@ -722,7 +721,7 @@ def finish_stacking(stc):
     return clf
 
 
-def _device_bases(clf, X, y, masks, folds_np, meta, plan, early, oof):
+def _device_bases(clf, X, y, masks, folds_np, meta, early, oof):
     """Host-synchronisation-free GBC / L1-LR fold batches for :func:`_fit_bases_concurrent`
     (:data:`DEVICE_BASES`).  ``fit(col, est)`` enqueues one estimator's 6 fits and its out-of-fold
     column (rows of fold k predicted by fold model k, written into ``meta[:, col]``), or returns None
@@ -754,10 +753,6 @@ def _device_bases(clf, X, y, masks, folds_np, meta, plan, early, oof):
     def gbc(col, est):
         clones = [est.clone() for _ in range(nb)]
         binned = box.pop("binned", None)
-        ba, cols = (plan or {}).get("bins_all"), (plan or {}).get("cols")
-        if binned is None and ba is not None and cols is not None and int(ba.max_bins) == int(clones[0].max_bins):
-            bm = ba.select(cols)     # binned under the LassoCV path (pipeline.develop), columns selected here
-            binned = (bm, bm.transform(Xc).contiguous())
         so = {}
         fit_gbdt_batch(clones, Xc, y, masks, binned=binned, deferred=deferred, finish={nb - 1}, state_out=so)
         st, raw0 = so["st"], so["raw0"].contiguous()
@@ -841,16 +836,6 @@ def _device_bases(clf, X, y, masks, folds_np, meta, plan, early, oof):
     return dict(fit=fit, deferred=deferred, post=post, keep=keep, prebin=prebin)
 
 
-def finish_prelaunched(pre: dict, timer: StageTimer = None) -> None:
-    """Finish a :func:`prelaunch_stack` state before its selection is confirmed (pipeline.develop,
-    while the LassoCV paths still run); :func:`fit_stacking` then only checks the selection — and
-    refits from scratch on a miss."""
-    stc = pre["state"]
-    stc["timer"] = timer or stc["timer"]
-    finish_stacking(stc)
-    pre["finished"] = True
-
-
 def fit_stacking(clf, X: torch.Tensor, y: torch.Tensor, timer: StageTimer = None, group=None, svc_group=None,
                  plan=None):
     pre = plan.get("prelaunch") if (plan is not None and group is None) else None
@@ -879,8 +864,6 @@ def fit_stacking(clf, X: torch.Tensor, y: torch.Tensor, timer: StageTimer = None
                 warnings.warn("device column selection differs from the host's; relaunching the stacking fit")
             pre = None
     LAST_PRELAUNCH["used"] = pre is not None
-    if pre is not None and pre.get("finished"):
-        return clf          # (finish_prelaunched already completed it)
     if pre is not None:
         stc = pre["state"]
         stc["timer"] = timer or stc["timer"]

@@ -1,6 +1,6 @@
 """Pieces of the host-synchronisation-free stacking fit that run on the CPU: the host-array bin fit
-and the column-subset bin map (pipeline.develop bins every candidate column under the LassoCV path,
-the GBC keeps the selected ones), and the deferred guard collector."""
+and the column-subset bin map (BinMapper.select: the bins of a column subset are a slice of the
+all-column fit), and the deferred guard collector."""
 import numpy as np
 import pytest
 import torch

@@ -890,8 +890,7 @@ def test_stump_ranks_device_matches_host(dev):
 
 def test_stacking_device_bases_match_synchronous(dev, monkeypatch):
     """The host-synchronisation-free GBC / L1-LR fold batches (stack_trainer.DEVICE_BASES: deferred
-    guards, device stump ranks, bins from the all-column map fitted under the LassoCV path, device
-    out-of-fold columns) give the synchronous round-4 fit: the same refit trees and coefficients bit
+    guards, device stump ranks, device out-of-fold columns) give the synchronous round-4 fit: the same refit trees and coefficients bit
     for bit, out-of-fold columns to the f32 tree-walk rounding of the old path (its forest kernel
     adds f32 leaf values; the device column is the f64 sum the reference's predict_proba forms)."""
     from hfens import pipeline
@@ -902,7 +901,6 @@ def test_stacking_device_bases_match_synchronous(dev, monkeypatch):
     out = {}
     for flag in (False, True):
         monkeypatch.setattr(stack_trainer, "DEVICE_BASES", flag)
-        monkeypatch.setattr(pipeline, "BIN_AHEAD", flag)   # (on: exercised here, off by default)
         out[flag] = pipeline.develop(args[0], args[1], args[2], args[3], names, device=dev)
     m0, m1 = out[False].model, out[True].model
     assert np.array_equal(out[False].selected, out[True].selected)
