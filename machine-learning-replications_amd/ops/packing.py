@@ -54,7 +54,7 @@ def pack_forest(feature, threshold, left, right, value, device) -> PackedForest:
                          right.to(torch.int32).cpu(), thr32.view(torch.int32)], dim=-1)
     nodes = nodes.reshape(T * K, 4).contiguous().to(device)
     vals = value.to(torch.float32).reshape(T * K).contiguous().to(device)
-    return PackedForest(nodes, vals, T, K, int(feature.max()))
+    return PackedForest(nodes, vals, T, K, int(feature.max()) if feature.numel() else -1)
 
 
 @dataclass

@@ -105,7 +105,7 @@ def tree_raw(x: torch.Tensor, feature: torch.Tensor, threshold: torch.Tensor, le
         go_left = fv <= threshold.gather(1, node)
         nxt = torch.where(go_left, left.long().gather(1, node), right.long().gather(1, node))
         node = torch.where(leaf, node, nxt)
-    v = value.to(torch.float64).reshape(T, -1).gather(1, node)          # [T, n]
+    v = value.to(torch.float64).reshape(T, feature.shape[1]).gather(1, node)          # [T, n]
     terms = torch.cat([torch.full((1, n), float(init), dtype=torch.float64, device=x.device), lr * v])
     return torch.cumsum(terms, 0)[-1]
 
@@ -143,7 +143,7 @@ def _stack_tail(x: torch.Tensor, dec: torch.Tensor, pk) -> torch.Tensor:
         nd = pk.forest.nodes.reshape(pk.forest.n_trees, pk.forest.max_nodes, 4)
         thr = nd[..., 3].contiguous().view(torch.float32).to(torch.float64)
         raw = tree_raw(x, nd[..., 0], thr, nd[..., 1], nd[..., 2],
-                       pk.forest.values.reshape(pk.forest.n_trees, -1), pk.gb_init, pk.gb_lr)
+                       pk.forest.values.reshape(pk.forest.n_trees, pk.forest.max_nodes), pk.gb_init, pk.gb_lr)
     p_gbc = torch.sigmoid(raw)
     p_lg = torch.sigmoid(x @ pk.lr_w.to(torch.float64) + pk.lr_b)
     w0, w1, w2 = pk.meta_w
@@ -269,3 +269,272 @@ def knn_impute1(fit, X, undecided_rel: float = 2.0 ** -45):
             near &= fit[donors, c][None, :] != vals[:, None]
             n_undecided += int(near.any(1)[ok].sum())
     return out[:, valid], mean_mask[:, valid], n_ties, n_undecided
+
+
+# ----------------------------------------------------------------------------- inference oracle
+# numpy longdouble, written from the published rules (libsvm svm_predict_values / sigmoid_predict /
+# multiclass_probability, sklearn's tree rule), on the UNPACKED model: nothing here imports torch
+# or ops.packing, so a wrong rounding direction, stump merge, base, pad or ‖sv‖² in the packing is
+# on one side of the comparison only.
+_U = 2.0 ** -24                 # f32 unit roundoff
+_TINY = 2.0 ** -125             # an f32 result flushed at the subnormal edge
+# Hardware transcendentals (v_exp_f32 behind __builtin_amdgcn_exp2f, and __expf = exp2(x·log2 e)),
+# measured once on an MI355X against long double on 2²² arguments (exp2: [−150, 1], a quarter of
+# them in [−2, 0.01]; __expf: [−100, 100], a quarter in [−8, 8]):
+#   exp2:   largest relative error of a normal result  EXP2_MEASURED · 2⁻²⁴; results below 2⁻¹²⁶
+#           are flushed to 0 (largest absolute error there 1.175e-38 = 2⁻¹²⁶, the _TINY term)
+#   __expf: largest relative error / (1 + |x|)          EXPF_MEASURED · 2⁻²⁴  (the f32 product
+#           x·log2 e is rounded before the exp2, which costs |x|·2⁻²⁴ relative); the whole f32
+#           sigmoid 1/(1 + __expf(−x)) was within 1.55 · 2⁻²⁴ absolute everywhere
+# The budgets use twice the measured values.
+EXP2_MEASURED = 1.40            # measured 1.3936
+EXPF_MEASURED = 1.27            # measured 1.2677
+EPS_EXP2 = 2 * EXP2_MEASURED * _U
+EPS_EXPF = 2 * EXPF_MEASURED * _U
+
+
+def _np():
+    import numpy as np
+    return np
+
+
+def _f32(a):
+    """The f32 rounding the kernels apply to rows and parameters, as longdouble."""
+    np = _np()
+    with np.errstate(over="ignore"):
+        return np.asarray(a).astype(np.float32).astype(np.longdouble)
+
+
+class StackSpec:
+    """The unpacked HF stack, f64 numpy: ``mean, scale [F]``, ``sv [m, F]``, ``coef [m]``, ``gamma``,
+    ``intercept``, ``A, B``, tree tables ``feature, threshold, left, right, value [T, K]`` (leaves
+    have feature < 0), ``init, lr``, ``lr_w [F]``, ``lr_b``, ``meta_w (svc, gbc, lg)``, ``meta_b``."""
+
+    def __init__(self, **kw):
+        np = _np()
+        for k in ("mean", "scale", "sv", "coef", "threshold", "value", "lr_w"):
+            setattr(self, k, np.asarray(kw.pop(k), dtype=np.float64))
+        for k in ("feature", "left", "right"):
+            setattr(self, k, np.asarray(kw.pop(k), dtype=np.int64))
+        for k in ("gamma", "intercept", "A", "B", "init", "lr", "lr_b", "meta_b"):
+            setattr(self, k, float(kw.pop(k)))
+        self.meta_w = tuple(float(w) for w in kw.pop("meta_w"))
+        assert not kw, f"unknown fields {sorted(kw)}"
+        self.F = int(self.mean.shape[0])
+
+
+def _rbf_core(z, dz, sv32, c32, gamma, b, x3):
+    """``dec = Σ c·exp(−γ·Σ(sv−z)²) + b`` by direct differences, and the forward bound of the
+    kernels' f32 evaluation of it through ``‖sv‖² + ‖z‖² − 2 sv·z`` (see :func:`stack_oracle`).
+    ``z``: exact longdouble rows, ``dz``: bound of the kernel's error on each ``z``."""
+    np = _np()
+    L = np.longdouble
+    n, F = z.shape
+    m = sv32.shape[0]
+    g2 = L(gamma) * L(LOG2E)
+    ln2 = np.log(L(2))
+    sn = (sv32 * sv32).sum(1)
+    asv, ac = np.abs(sv32), np.abs(c32)
+    dec = np.zeros(n, dtype=L)
+    bud = np.zeros(n, dtype=L)
+    step = max(1, (1 << 20) // max(1, m * F))
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for s in range(0, n, step):
+            zz, dzz = z[s:s + step], dz[s:s + step]
+            diff = sv32[None, :, :] - zz[:, None, :]
+            d2 = (diff * diff).sum(-1)
+            cross = (asv[None, :, :] * np.abs(zz)[:, None, :]).sum(-1)
+            mag = sn[None, :] + (zz * zz).sum(-1)[:, None] + 2 * cross
+            dd2 = (F + 3) * _U * mag + 2 * (np.abs(diff) * dzz[:, None, :]).sum(-1)
+            if x3:
+                dd2 = dd2 + 2 * 3 * _U * cross
+            k = np.exp(-L(gamma) * d2)
+            # exponent (base 2) error: the distance error and the f32 roundings of −γ·log2 e
+            de = g2 * dd2 + 2 * _U * g2 * d2
+            dk = np.where(k > 0, k * (ln2 * de + EPS_EXP2), 0) + _TINY
+            ck = ac[None, :] * k
+            d = (c32[None, :] * k).sum(-1) + L(b)
+            dec[s:s + step] = d
+            bud[s:s + step] = (ac[None, :] * dk).sum(-1) + m * _U * ck.sum(-1) + 2 * _U * (np.abs(d) + abs(b))
+    return dec, 2 * bud
+
+
+def rbf_oracle(z, sv, coef, gamma, intercept):
+    """``rbf_decision``'s oracle: rows, SVs and coefficients rounded to f32 here, the distance
+    direct.  Returns ``(dec, Δdec)`` per row (longdouble)."""
+    np = _np()
+    z32 = _f32(z)
+    return _rbf_core(z32, np.zeros_like(z32), _f32(sv), _f32(coef), gamma, float(np.float32(intercept)), False)
+
+
+def couple_oracle(dec, A, B, clip=True):
+    """libsvm ``sigmoid_predict`` + ``multiclass_probability`` (k = 2, eps = 0.005/k, at most 100
+    iterations) step by step in longdouble.  Returns ``(p1, it)``: P(class 1) and the number of
+    update sweeps done before the stopping test held."""
+    np = _np()
+    L = np.longdouble
+    dec = np.asarray(dec, dtype=L)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        f = dec * L(A) + L(B)
+        e = np.exp(-np.abs(f))
+        r01 = np.where(f >= 0, e / (1 + e), 1 / (1 + e))
+        if clip:
+            lo = L(np.float64(1e-7))
+            r01 = np.minimum(np.maximum(r01, lo), L(np.float64(1) - np.float64(1e-7)))
+        r = [[None, r01], [1 - r01, None]]                 # r[i][j] = P(i | {i, j})
+        Q = [[r[1][0] * r[1][0], -r[1][0] * r[0][1]], [-r[0][1] * r[1][0], r[0][1] * r[0][1]]]
+        p = [np.full(dec.shape, L(0.5)), np.full(dec.shape, L(0.5))]
+        it = np.zeros(dec.shape, dtype=np.int64)
+        active = np.ones(dec.shape, dtype=bool)
+        for _ in range(100):
+            Qp = [Q[t][0] * p[0] + Q[t][1] * p[1] for t in range(2)]
+            pQp = p[0] * Qp[0] + p[1] * Qp[1]
+            err = np.maximum(np.abs(Qp[0] - pQp), np.abs(Qp[1] - pQp))
+            active &= ~(err < L(0.005) / 2)
+            if not active.any():
+                break
+            q = [x.copy() for x in p]
+            for t in range(2):
+                diff = (-Qp[t] + pQp) / Q[t][t]
+                q[t] = q[t] + diff
+                pQp = (pQp + diff * (diff * Q[t][t] + 2 * Qp[t])) / (1 + diff) / (1 + diff)
+                for j in range(2):
+                    Qp[j] = (Qp[j] + diff * Q[t][j]) / (1 + diff)
+                    q[j] = q[j] / (1 + diff)
+            p = [np.where(active, q[j], p[j]) for j in range(2)]
+            it += active
+    return p[1], it
+
+
+def proba_oracle(dec, A, B, ddec=None):
+    """P(class 1) of a decision value the kernel holds with error ≤ ``ddec``.  The coupling's
+    stopping rule makes p a step function of the iteration count, so p(dec) jumps (by up to
+    5·10⁻³) where the count changes: a row whose count differs over ``dec − δ, dec, dec + δ`` is
+    ``undecided`` — no tolerance short of the jump can referee it; otherwise Δp is the largest of
+    the three differences plus the f32 cast of the result.  δ is at least 2⁻⁴⁰·(1 + |dec|), the
+    kernels' own f64 evaluation of A·dec + B and of the sigmoid.  Returns ``(p, it, Δp, undecided)``."""
+    np = _np()
+    L = np.longdouble
+    dec = np.asarray(dec, dtype=L)
+    d = np.maximum(np.zeros_like(dec) if ddec is None else np.asarray(ddec, dtype=L),
+                   L(2.0 ** -40) * (1 + np.abs(dec)))
+    p, it = couple_oracle(dec, A, B)
+    pl, il = couple_oracle(dec - d, A, B)
+    ph, ih = couple_oracle(dec + d, A, B)
+    und = (il != it) | (ih != it)
+    dp = np.maximum(np.abs(pl - p), np.abs(ph - p)) + 2 * _U * p
+    return p, it, dp, und
+
+
+def _leaf_sums(X, feature, threshold, left, right, value):
+    """Per row: Σ_t value_t[leaf_t] (longdouble, unrounded values) under sklearn's rule
+    ``float64(float32(x)) <= threshold64`` → left, and Σ_t max_k |value_t[k]|."""
+    np = _np()
+    L = np.longdouble
+    with np.errstate(over="ignore"):
+        x = np.asarray(X).astype(np.float32).astype(np.float64)
+    n = x.shape[0]
+    T = feature.shape[0]
+    acc = np.zeros(n, dtype=L)
+    rows = np.arange(n)
+    for t in range(T):
+        node = np.zeros(n, dtype=np.int64)
+        for _ in range(feature.shape[1]):
+            f = feature[t, node]
+            leaf = f < 0
+            if leaf.all():
+                break
+            go = x[rows, np.maximum(f, 0)] <= threshold[t, node]
+            node = np.where(leaf, node, np.where(go, left[t, node], right[t, node]))
+        acc += value[t, node].astype(L)
+    vmax = np.abs(value).max(1).sum() if T else 0.0
+    return acc, float(vmax)
+
+
+def forest_oracle(X, feature, threshold, left, right, value, init, lr):
+    """``init + lr·Σ_t value_t[leaf_t(x)]`` with the leaf chosen on the unrounded f64 thresholds,
+    and its budget: the kernels hold f32 leaf values (or f32 stump deltas lr·(v_r − v_l) and an
+    f32 base), add them one by one (T roundings on a partial sum ≤ S) and finish with
+    init + lr·raw: 2·(T + 4)·2⁻²⁴·S with S = |init| + 2·lr·Σ_t max_k|value_t[k]|."""
+    np = _np()
+    acc, vmax = _leaf_sums(X, *(np.asarray(a) for a in (feature, threshold, left, right, value)))
+    raw = np.longdouble(init) + np.longdouble(lr) * acc
+    S = abs(init) + 2 * abs(lr) * vmax
+    return raw, np.full(raw.shape, 2 * (feature.shape[0] + 4) * _U * S, dtype=np.longdouble)
+
+
+def _sigmoid_budget(v, dv):
+    """σ(v) and the bound of ``1/(1 + __expf(−v))`` evaluated in f32 at an argument off by ≤ dv:
+    slope·(dv + (1 + |v|)·EPS_EXPF) + 2 roundings, the slope σ' taken at the point of [v−dv, v+dv]
+    nearest 0."""
+    np = _np()
+    L = np.longdouble
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        s = 1 / (1 + np.exp(-v))
+        a = np.maximum(np.abs(v) - dv, 0)
+        sl = np.exp(-a) / (1 + np.exp(-a)) ** 2
+        return s, 2 * (sl * (dv + (1 + np.abs(v)) * L(EPS_EXPF)) + 2 * _U * s) + _TINY
+
+
+def stack_oracle(M, X, x3=True):
+    """The fused stack on the unpacked model ``M`` (:class:`StackSpec`), per row of ``X``, in
+    longdouble — with every stage's forward error budget for the f32 kernels.
+
+    Semantics (defined here, not read off the kernels): rows, scaler mean, 1/scale, SVs, dual
+    coefficients, LR weights and the scalar parameters are rounded to f32 (what the kernels hold);
+    ``z = (x − mean)·(1/scale)`` exactly from those; the distance is the direct ``Σ(sv − z)²``; trees
+    follow ``float64(float32(x)) <= threshold64`` on the unrounded thresholds (stumps too) with
+    unrounded leaf values; sigmoid and coupling are libsvm's (:func:`couple_oracle`).
+
+    Budgets, first order, u = 2⁻²⁴, every stage × 2 for the second-order terms:
+      z        two roundings (subtract, scale): |δz_f| ≤ 2u|z_f|
+      d²       2Σ|sv_f − z_f||δz_f| + (F + 3)u·(‖sv‖² + ‖z‖² + 2Σ|sv_f||z_f|) for the F-term fma/MFMA
+               chains of ‖sv‖², ‖z‖², sv·z and the 3 operations joining them; the X3 path's dropped
+               piece products add 3u·Σ|sv_f||z_f| to sv·z (twice that to d²)
+      k        k·(ln 2·(γ log2 e·δd² + 2u·|exponent|) + EPS_EXP2) + 2⁻¹²⁵ (−γ·log2 e is held in f32)
+      dec      Σ|c_j|δk_j + m·u·Σ|c_j|k_j (m accumulations of c·k) + 2u(|dec| + |b|)
+      p_svc    :func:`proba_oracle` at dec ± δdec (``undecided`` where the iteration count changes)
+      raw_gbc  :func:`forest_oracle`
+      p_lg     F·u·(|b| + Σ|x_f w_f|) for the LR dot, then the sigmoid
+      σ        :func:`_sigmoid_budget`
+      P        Σ|w_i|Δp_i + 4u(|b_m| + Σ|w_i|p_i) through the meta sigmoid (slope ≤ ¼)
+    ``x3=False`` leaves the dropped-product term out: the budget of the f32-MFMA path.
+
+    Where the budgets do not apply (rows outside the domain; the kernels and the f64 host paths
+    differ there and no tolerance referees it — known, kept, and documented here):
+      * a row whose scaled feature ``(x − mean)·(1/scale)`` or LR product ``x_f·w_f`` overflows f32
+        (|·| > 3.4e38): ``stack_infer`` holds z in f32, so z = ±inf, the expanded distance is inf − inf
+        and the row's output is NaN, while ``reference.stack_infer`` (f64) stays finite, and so
+        does this oracle (z in longdouble).  The ±3e38 threshold-edge inputs of the tests therefore
+        scale by 2⁻⁷⁰ and carry zero LR weights: they are about the trees.  Such a row never disturbs another row
+        (tests/test_infer_reference_gpu.py, row isolation).
+      * a NaN feature: every comparison is false, so the stump table adds no delta (the row goes
+        LEFT) while the tree walk of the same stumps fails ``x <= thr`` and goes RIGHT; P is NaN either
+        way through z.  The predict paths impute before inference; rows must be finite.
+    Returns a dict of longdouble arrays: dec, it, p_svc, raw_gbc, p_gbc, p_lg, P, their budgets
+    d_dec, d_p_svc, d_raw_gbc, d_p_gbc, d_p_lg, d_P, and the boolean ``undecided``."""
+    np = _np()
+    L = np.longdouble
+    x32 = _f32(X)
+    F = M.F
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        z = (x32 - _f32(M.mean)) * _f32(1.0 / M.scale)
+        dec, d_dec = _rbf_core(z, 2 * _U * np.abs(z), _f32(M.sv), _f32(M.coef), M.gamma,
+                               float(np.float32(M.intercept)), x3)
+        p_svc, it, d_p_svc, und = proba_oracle(dec, M.A, M.B, d_dec)
+        raw, d_raw = forest_oracle(X, M.feature, M.threshold, M.left, M.right, M.value, M.init, M.lr)
+        p_gbc, d_p_gbc = _sigmoid_budget(raw, d_raw)
+        w32 = _f32(M.lr_w)
+        b_lr = L(np.float32(M.lr_b))
+        lin = (x32 * w32[None, :]).sum(1) + b_lr
+        d_lin = 2 * F * _U * (abs(b_lr) + (np.abs(x32) * np.abs(w32)[None, :]).sum(1))
+        p_lg, d_p_lg = _sigmoid_budget(lin, d_lin)
+        w = [L(np.float32(v)) for v in M.meta_w]
+        mb = L(np.float32(M.meta_b))
+        mm = mb + w[0] * p_svc + w[1] * p_gbc + w[2] * p_lg
+        d_mm = abs(w[0]) * d_p_svc + abs(w[1]) * d_p_gbc + abs(w[2]) * d_p_lg + \
+            2 * 4 * _U * (abs(mb) + abs(w[0]) * p_svc + abs(w[1]) * p_gbc + abs(w[2]) * p_lg)
+        P = 1 / (1 + np.exp(-mm))
+        d_P = 0.25 * (d_mm + 2 * (1 + np.abs(mm)) * L(EPS_EXPF)) + 4 * _U * P
+    return dict(dec=dec, it=it, p_svc=p_svc, raw_gbc=raw, p_gbc=p_gbc, p_lg=p_lg, P=P, d_dec=d_dec,
+                d_p_svc=d_p_svc, d_raw_gbc=d_raw, d_p_gbc=d_p_gbc, d_p_lg=d_p_lg, d_P=d_P, undecided=und)

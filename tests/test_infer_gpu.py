@@ -20,8 +20,11 @@ def test_rbf_decision(dev, n, m, F):
     gamma = 1.0 / F
     want = ref.rbf_decision(z, sv, coef, gamma, 0.25)
     got = ops.rbf_decision(z.to(dev), sv.to(dev), coef.to(dev), gamma, 0.25).cpu().double()
-    scale = coef.abs().sum().item()
-    assert torch.allclose(got, want, atol=2e-6 * scale, rtol=0)
+    # per row: the oracle's forward budget (ops.reference.rbf_oracle), never above the former constant
+    dec, budget = ref.rbf_oracle(z.numpy(), sv.numpy(), coef.numpy(), gamma, 0.25)
+    tol = np.minimum(budget.astype(np.float64), 2e-6 * coef.abs().sum().item())
+    assert (np.abs(got.numpy() - want.numpy()) <= tol).all()
+    assert (np.abs(got.numpy() - dec.astype(np.float64)) <= tol).all()
 
 
 def test_svc_proba1(dev):
@@ -54,7 +57,10 @@ def test_forest_raw(dev, T, depth, F):
     x = torch.randn(2000, F, dtype=torch.float64)
     want = ref.tree_raw(x, feat, thr, left, right, val, -1.3, 0.1)
     got = ops.tree_raw(x.to(dev), feat, thr, left, right, val, -1.3, 0.1).cpu().double()
-    assert torch.allclose(got, want, atol=1e-5)
+    raw, budget = ref.forest_oracle(x.numpy(), *(a.numpy() for a in (feat, thr, left, right, val)), -1.3, 0.1)
+    tol = np.minimum(budget.astype(np.float64), 1e-5)    # the oracle's budget, never above the former constant
+    assert (np.abs(got.numpy() - want.numpy()) <= tol).all()
+    assert (np.abs(got.numpy() - raw.astype(np.float64)) <= tol).all()
 
 
 def test_checkpoint_stack_on_gpu(dev, ckpt_path):

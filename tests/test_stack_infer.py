@@ -23,7 +23,8 @@ def _patients(n, seed=1):
     return torch.as_tensor(X)
 
 
-def _random_pstack(F, m, T, depth, device, seed=0, stumps=True):
+def _random_model(F, m, T, depth, seed=0):
+    """The unpacked random stack: (sv, coef, [feature, threshold, left, right, value], mean, inv_scale, lr_w)."""
     g = torch.Generator().manual_seed(seed)
     sv = torch.randn(m, F, generator=g, dtype=torch.float64)
     coef = torch.randn(m, generator=g, dtype=torch.float64) / m ** 0.5
@@ -40,14 +41,28 @@ def _random_pstack(F, m, T, depth, device, seed=0, stumps=True):
             thr[t, i] = rng.normal()
             left[t, i], right[t, i] = 2 * i + 1, 2 * i + 2
     tabs = [torch.as_tensor(a) for a in (feat, thr, left, right, val)]
+    mean, inv_scale = 0.1 * torch.randn(F, generator=g), 0.5 + torch.rand(F, generator=g)
+    return sv, coef, tabs, mean, inv_scale, 0.3 * torch.randn(F, generator=g)
+
+
+def _random_pstack(F, m, T, depth, device, seed=0, stumps=True):
+    sv, coef, tabs, mean, inv_scale, lr_w = _random_model(F, m, T, depth, seed)
     f = pack_forest(*tabs, device)
     return PackedStack(
-        F=F, sv=pack_svs(sv, coef, device),
-        mean=(0.1 * torch.randn(F, generator=g)).to(device), inv_scale=(0.5 + torch.rand(F, generator=g)).to(device),
+        F=F, sv=pack_svs(sv, coef, device), mean=mean.to(device), inv_scale=inv_scale.to(device),
         gamma=0.5 / F, svc_b=0.2, probA=-1.7, probB=0.1, forest=f,
         stumps=stump_table(*tabs, -0.4, 0.1, F, device) if stumps else None, gb_init=-0.4, gb_lr=0.1,
-        lr_w=(0.3 * torch.randn(F, generator=g)).to(device), lr_b=-0.2,
-        meta_w=(1.9, 0.5, 2.7), meta_b=-2.0)
+        lr_w=lr_w.to(device), lr_b=-0.2, meta_w=(1.9, 0.5, 2.7), meta_b=-2.0)
+
+
+def _random_spec(F, m, T, depth, seed=0):
+    """The same model, unpacked, for the longdouble oracle (1/inv_scale rounds back to inv_scale in f32)."""
+    sv, coef, tabs, mean, inv_scale, lr_w = _random_model(F, m, T, depth, seed)
+    feat, thr, left, right, val = (a.numpy() for a in tabs)
+    return ref.StackSpec(mean=mean.numpy(), scale=1.0 / inv_scale.double().numpy(), sv=sv.numpy(), coef=coef.numpy(),
+                         gamma=0.5 / F, intercept=0.2, A=-1.7, B=0.1, feature=feat, threshold=thr, left=left,
+                         right=right, value=val, init=-0.4, lr=0.1, lr_w=lr_w.numpy(), lr_b=-0.2,
+                         meta_w=(1.9, 0.5, 2.7), meta_b=-2.0)
 
 
 def test_fused_reference_matches_per_model_path(ckpt_path):
@@ -113,6 +128,16 @@ def test_stack_infer_random(dev, F, m, T, depth, grid, stumps):
     want = ref.stack_infer(x.to(torch.float32), pk_h)
     got = ops.stack_infer(x.to(dev), pk_d, grid=grid).cpu().double()
     assert torch.allclose(got, want, atol=5e-6)
+    # per decided row: the oracle's forward budget for the launched path (ops.reference.stack_oracle on
+    # the unpacked model), never above the former constant — on the first and last tile and a sample
+    # of the rows between (m = 6000 SVs in longdouble: all 5000 rows would take a minute)
+    from test_infer_reference import assert_stack
+    from test_infer_reference_gpu import stack_path
+    rows = np.unique(np.concatenate([np.arange(64), np.arange(64, 4936, 38), np.arange(4936, 5000)]))
+    path = stack_path(pk_h)
+    orc = ref.stack_oracle(_random_spec(F, m, T, depth, seed=F + m), x.numpy()[rows], x3=path.kind == "X3")
+    orc["d_P"] = np.minimum(orc["d_P"], 5e-6)
+    assert_stack(got.numpy()[rows], orc, f"random F={F} m={m} T={T} depth={depth} path={tuple(path)}")
 
 
 @pytest.mark.gpu
