@@ -10,7 +10,10 @@ instead of ``plt.show()`` on a headless node, ``--no-plots`` to skip).  Those
 ``.mat`` files are private, so when they are absent a Table-S1-shaped synthetic
 cohort is generated (``--rows``, ``--features``).  Extras: ``--device cuda``, ``--save-model``
 (writes the sklearn-0.23.2 ``.pkl`` layout that ``predict_hf.py`` reads),
-``--timings``; under ``torchrun`` the development rows are sharded over ranks.
+``--timings``, ``--bootstrap N`` (percentile confidence intervals of the held-out AUROC, AP
+and thresholded rates from N bootstrap resamples, and a bootstrap band on the ROC figure;
+``--bootstrap-seed``, ``--stratified``); under ``torchrun`` the development rows are sharded
+over ranks.
 """
 from __future__ import annotations
 
@@ -38,7 +41,14 @@ def main(argv=None, script_dir=None) -> int:
     ap.add_argument("--lr-optimum", action="store_true",
                     help="solve 'lg' to its exact optimum on the device instead of reproducing liblinear's "
                          "default-tolerance iterate and seed draw (the reference's T:31/T:46 behaviour)")
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="N",
+                    help="bootstrap the held-out rows N times: confidence intervals and a ROC band (default 0 = off)")
+    ap.add_argument("--bootstrap-seed", type=int, default=2020)
+    ap.add_argument("--stratified", action="store_true",
+                    help="resample positives and negatives separately (class totals fixed)")
     a = ap.parse_args(argv)
+    if a.bootstrap < 0:
+        ap.error("--bootstrap must be >= 0")
     if a.no_plots:
         a.plots = None
 
@@ -78,7 +88,7 @@ def main(argv=None, script_dir=None) -> int:
     # are drawn from it, six times, in the stacking fit's order
     np.random.seed(cfg.seed)
     res = develop(X_dev, y_dev, X_sel, y_sel, names, device=device, group=group, cfg=cfg)
-    if a.plots:
+    if a.plots or a.bootstrap:
         # collectives on EVERY rank (before the rank-0 block); only rank 0 draws
         p_all = res.proba_sel
         y_all = torch.as_tensor(y_sel, device=p_all.device)
@@ -91,10 +101,21 @@ def main(argv=None, script_dir=None) -> int:
         print("number of features = ", len(res.selected_names))
         print(res.report)
         print(f"AUROC = {res.scores['auroc']:.4f}   AP = {res.scores['average_precision']:.4f}")
+        ci = None
+        if a.bootstrap:
+            ci = metrics.bootstrap_ci(y_all, p_all, n_boot=a.bootstrap, seed=a.bootstrap_seed,
+                                      stratified=a.stratified)
+            lvl = f"{100 * (1 - ci['alpha']):g}% CI"
+
+            def fmt(k):
+                return f"{ci[k]['point']:.4f} ({lvl} {ci[k]['lo']:.4f}\u2013{ci[k]['hi']:.4f})"
+            print(f"AUROC = {fmt('auroc')}   AP = {fmt('average_precision')}")
+            print("   ".join(f"{k} = {fmt(k)}" for k in ("precision", "recall", "specificity", "accuracy")))
         if a.timings:
             print(res.timer.table())
         if a.plots:
-            print("plots:", metrics.save_plots(y_all, p_all, a.plots))
+            band = (ci["fpr_grid"], ci["tpr_lo"], ci["tpr_hi"]) if ci else None
+            print("plots:", metrics.save_plots(y_all, p_all, a.plots, band=band))
         if a.save_model:
             from ..io.checkpoint import save_checkpoint
             model = res.model
@@ -103,8 +124,11 @@ def main(argv=None, script_dir=None) -> int:
             print(f"saved {a.save_model}")
         if a.json:
             with open(a.json, "a") as f:
-                f.write(json.dumps({"source": source, "n_train": res.n_train, "scores": res.scores,
-                                    "timings": dict(res.timer.times), "world_size": world}) + "\n")
+                line = {"source": source, "n_train": res.n_train, "scores": res.scores,
+                        "timings": dict(res.timer.times), "world_size": world}
+                if ci is not None:
+                    line["bootstrap"] = ci
+                f.write(json.dumps(line) + "\n")
     pdist.shutdown()
     return 0
 

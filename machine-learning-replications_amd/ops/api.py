@@ -8,7 +8,7 @@ from . import reference as ref
 from .packing import pack_forest, pack_stack, pack_svs
 
 __all__ = ["rbf_decision", "svc_proba1", "tree_raw", "expit", "pack_svs", "pack_forest", "pack_stack",
-           "stack_infer", "stack_shapley", "weighted_moments"]
+           "stack_infer", "stack_shapley", "weighted_moments", "bootstrap_metrics"]
 
 
 def _c(t: torch.Tensor, dtype) -> torch.Tensor:
@@ -161,6 +161,96 @@ def _stack_shapley_device(x, background, pk, return_values: bool, grid: int):
             base = v[0, 0].clone()
     out = (phi, base, pred)
     return out + (v_all,) if return_values else out
+
+
+BOOTSTRAP_MAX_B = 1 << 24          # the replicate index shares the draw counter: b < 2^24
+BOOTSTRAP_MAX_N = 1 << 25          # keeps the doubled AUROC numerator below 2^53
+BOOTSTRAP_LDS_ROWS = 20000         # rows whose two u32 arrays fit the CU's 160 KiB LDS (csrc/bootstrap.hip)
+BOOTSTRAP_WS_BYTES = 1 << 30       # byte budget of the global workspace above that (8n bytes per resident workgroup)
+_BOOTSTRAP_FORCE_GLOBAL = False    # tests: take the global-workspace path below the LDS limit too
+
+
+def bootstrap_metrics(y, score, n_boot: int, *, seed: int = 0, stratified: bool = False,
+                      threshold: float = 0.5, grid_points: int = 101, b0: int = 0, b1=None,
+                      grid: int = 0, stream=None):
+    """Bootstrap replicates ``b0:b1`` (default all ``n_boot``) of the held-out metrics of binary
+    labels ``y [n]`` and scores ``score [n]`` (f32 or f64) on one device.
+
+    Replicate b resamples n rows with replacement by the counter-based law of
+    ``csrc/bootstrap.hip`` (plain, or ``stratified``: P positives and N negatives drawn within
+    their class), so it does not depend on the range, grid or device it is computed in.  Returns
+    ``auroc [B]`` = ``a2 / (2·P_b·N_b)`` and ``ap [B]`` (f64), the exact doubled AUROC numerator
+    ``a2 [B]``, the class totals ``pn [B, 2]``, the confusion counts ``conf [B, 4]`` = TP, FP, FN,
+    TN at ``score > threshold`` (all int64) and ``tpr [B, grid_points]`` (f64): the replicate's ROC
+    read at FPR = g/(grid_points − 1), the upper point of a vertical run.  A degenerate replicate
+    (``P_b = 0`` or ``N_b = 0``; plain mode only) has NaN ``auroc``, ``ap`` and ``tpr``.
+    ``stream``, if given, is a raw HIP stream handle: everything is enqueued on it."""
+    if y.dim() != 1 or score.dim() != 1 or y.numel() != score.numel():
+        raise ValueError(f"bootstrap_metrics: y {tuple(y.shape)} and score {tuple(score.shape)} must be "
+                         "1-D of one length")
+    n = score.numel()
+    if n == 0:
+        raise ValueError("bootstrap_metrics: y and score are empty (n = 0)")
+    if n > BOOTSTRAP_MAX_N:
+        raise ValueError(f"bootstrap_metrics: y has {n} rows, the limit is n <= {BOOTSTRAP_MAX_N}")
+    if y.device != score.device:
+        raise ValueError("bootstrap_metrics: y and score must be on the same device")
+    if not score.is_floating_point() or not bool(torch.isfinite(score).all()):
+        raise ValueError("bootstrap_metrics: score must be finite floating point")
+    if not bool(((y == 0) | (y == 1)).all()):
+        raise ValueError("bootstrap_metrics: y must hold labels 0 and 1 only")
+    n_boot = int(n_boot)
+    if not 1 <= n_boot <= BOOTSTRAP_MAX_B:
+        raise ValueError(f"bootstrap_metrics: n_boot = {n_boot} outside 1..{BOOTSTRAP_MAX_B}")
+    b1 = n_boot if b1 is None else int(b1)
+    b0 = int(b0)
+    if not 0 <= b0 <= b1 <= n_boot:
+        raise ValueError(f"bootstrap_metrics: b0:b1 = {b0}:{b1} is not a range within 0..n_boot = {n_boot}")
+    G = int(grid_points)
+    if not 2 <= G <= 65536:
+        raise ValueError(f"bootstrap_metrics: grid_points = {G} outside 2..65536")
+    if threshold != threshold:
+        raise ValueError("bootstrap_metrics: threshold is NaN")
+    if stratified:
+        P = int((y == 1).sum())
+        if P == 0 or P == n:
+            raise ValueError("bootstrap_metrics: stratified resampling needs both classes in y")
+    kw = dict(seed=seed, stratified=bool(stratified), threshold=float(threshold), grid_points=G, b0=b0, b1=b1)
+    if not score.is_cuda:
+        return ref.bootstrap_metrics(y, score, n_boot, **kw)
+    if stream is not None:
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=score.device)):
+            return _bootstrap_device(y, score, grid=grid, **kw)
+    return _bootstrap_device(y, score, grid=grid, **kw)
+
+
+def _bootstrap_device(y, score, *, seed, stratified, threshold, grid_points, b0, b1, grid):
+    """Validated ``cuda`` inputs; everything is enqueued on torch's current stream."""
+    from . import ext, stream_ptr
+    dev = score.device
+    pl = ref.BootstrapPlan(y, score, stratified, threshold)
+    n, G, B = pl.n, grid_points, b1 - b0
+    f64, i64 = torch.float64, torch.int64
+    auroc = torch.empty(B, dtype=f64, device=dev)
+    ap = torch.empty(B, dtype=f64, device=dev)
+    a2 = torch.empty(B, dtype=i64, device=dev)
+    pn = torch.empty(B, 2, dtype=i64, device=dev)
+    conf = torch.empty(B, 4, dtype=i64, device=dev)
+    tpr = torch.empty(B, G, dtype=f64, device=dev)
+    if B == 0:
+        return auroc, ap, a2, pn, conf, tpr
+    use_lds = n <= BOOTSTRAP_LDS_ROWS and not _BOOTSTRAP_FORCE_GLOBAL
+    ws, slices = None, 0
+    if not use_lds:
+        ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+        slices = max(1, min(B, 2 * ncu, BOOTSTRAP_WS_BYTES // (8 * n)))
+        ws = torch.empty(slices, 2 * n, dtype=torch.int32, device=dev)
+    ext().bootstrap_metrics(pl.y.data_ptr(), pl.gfirst.data_ptr(), pl.glast.data_ptr(), pl.map.data_ptr(), n,
+                            pl.p0, pl.k0, G, ref._seed_i64(seed), b0, B, int(use_lds),
+                            ws.data_ptr() if ws is not None else 0, slices, auroc.data_ptr(), ap.data_ptr(),
+                            a2.data_ptr(), pn.data_ptr(), conf.data_ptr(), tpr.data_ptr(), int(grid),
+                            stream_ptr(dev))
+    return auroc, ap, a2, pn, conf, tpr
 
 
 def expit(x):

@@ -204,4 +204,9 @@ HFENS_OP(knn_apply, (uintptr_t X, long long n, int F, uintptr_t rows, uintptr_t 
                      uintptr_t colmean, uintptr_t cnt, uintptr_t stream))
 HFENS_OP(host_store, (uintptr_t src, uintptr_t dst_host, long long n, int elem_bytes, uintptr_t stream))
 HFENS_OP(rbf_f64, (uintptr_t Z, long long l, uintptr_t L, int m, int F, double gamma, uintptr_t out, uintptr_t stream))
+HFENS_OP(bootstrap_lds_rows, (uintptr_t out))
+HFENS_OP(bootstrap_metrics, (uintptr_t y, uintptr_t gfirst, uintptr_t glast, uintptr_t map, long long n, long long p0,
+                             long long k0, int G, long long seed, long long b0, long long nb, int use_lds,
+                             uintptr_t ws, long long ws_slices, uintptr_t auroc, uintptr_t ap, uintptr_t a2,
+                             uintptr_t pn, uintptr_t conf, uintptr_t tpr, int grid, uintptr_t stream))
 #undef HFENS_OP

@@ -538,3 +538,231 @@ def stack_oracle(M, X, x3=True):
         d_P = 0.25 * (d_mm + 2 * (1 + np.abs(mm)) * L(EPS_EXPF)) + 4 * _U * P
     return dict(dec=dec, it=it, p_svc=p_svc, raw_gbc=raw, p_gbc=p_gbc, p_lg=p_lg, P=P, d_dec=d_dec,
                 d_p_svc=d_p_svc, d_raw_gbc=d_raw, d_p_gbc=d_p_gbc, d_p_lg=d_p_lg, d_P=d_P, undecided=und)
+
+
+# ---- bootstrap of the held-out metrics ------------------------------------------------------------
+# Resampling law (shared by this mirror, the kernel in csrc/bootstrap.hip and the oracle below):
+# draw j of replicate b over a stratum of m rows is row r of it,
+#     u = splitmix64(seed ^ splitmix64((b << 40) ^ j)),   r = ((u >> 32)·m) >> 32   ∈ [0, m)
+# (bias ≤ m/2^32).  Plain: j ∈ [0, n), m = n.  Stratified: j < P draws the r-th positive (m = P),
+# j ≥ P the r-th negative (m = N), both numbered in original row order.
+
+def _splitmix64_t(x: torch.Tensor) -> torch.Tensor:
+    """splitmix64 on int64 tensors (two's-complement wraparound = mod 2^64)."""
+    def srl(v, k):
+        return (v >> k) & ((1 << (64 - k)) - 1)
+
+    def c(v):
+        return torch.tensor(v - (1 << 64), dtype=torch.int64, device=x.device)
+    x = x + c(0x9E3779B97F4A7C15)
+    x = (x ^ srl(x, 30)) * c(0xBF58476D1CE4E5B9)
+    x = (x ^ srl(x, 27)) * c(0x94D049BB133111EB)
+    return x ^ srl(x, 31)
+
+
+def _seed_i64(seed: int) -> int:
+    s = int(seed) & ((1 << 64) - 1)
+    return s - (1 << 64) if s >= (1 << 63) else s
+
+
+class BootstrapPlan:
+    """What is prepared once per call: the descending stable score order and, in it, the labels
+    ``y`` (uint8), every row's tie-group ``gfirst``/``glast`` (int32), ``map`` (int32: drawn row →
+    position in the order; stratified: the positives' positions, then the negatives'), ``p0``
+    (draws j < p0 take the first stratum; plain: n) and ``k0`` = number of rows scoring > threshold."""
+
+    def __init__(self, y: torch.Tensor, score: torch.Tensor, stratified: bool, threshold: float):
+        dev = score.device
+        n = score.numel()
+        s = score.to(torch.float64)
+        order = torch.argsort(s, descending=True, stable=True)
+        ss = s[order]
+        pos = y.to(dev) > 0
+        start = torch.ones(n, dtype=torch.bool, device=dev)
+        start[1:] = ss[1:] != ss[:-1]
+        firsts = torch.nonzero(start).squeeze(1)
+        gid = torch.cumsum(start.to(torch.int64), 0) - 1
+        lasts = torch.cat([firsts[1:] - 1, torch.tensor([n - 1], device=dev)])
+        rank = torch.empty(n, dtype=torch.int64, device=dev)
+        rank[order] = torch.arange(n, device=dev)
+        self.n = n
+        self.y = pos[order].to(torch.uint8).contiguous()
+        self.gfirst = firsts[gid].to(torch.int32).contiguous()
+        self.glast = lasts[gid].to(torch.int32).contiguous()
+        self.P = int(pos.sum())
+        if stratified:
+            self.map = torch.cat([rank[pos], rank[~pos]]).to(torch.int32).contiguous()
+            self.p0 = self.P
+        else:
+            self.map = rank.to(torch.int32).contiguous()
+            self.p0 = n
+        self.k0 = int((s > threshold).sum())
+
+
+def bootstrap_metrics(y: torch.Tensor, score: torch.Tensor, n_boot: int, *, seed: int = 0,
+                      stratified: bool = False, threshold: float = 0.5, grid_points: int = 101,
+                      b0: int = 0, b1=None, chunk_elems: int = 1 << 22):
+    """Vectorised torch mirror of the bootstrap kernel (and the host path of
+    ``ops.bootstrap_metrics``, which validates): counts by ``bincount`` over the draws of the law
+    above, then the kernel's formulas in int64 and f64.  Returns ``auroc [B]``, ``ap [B]`` (f64),
+    ``a2 [B]``, ``pn [B, 2]``, ``conf [B, 4]`` (int64; TP FP FN TN) and ``tpr [B, G]`` (f64) for
+    replicates ``b0:b1``.  A replicate with ``P_b = 0`` or ``N_b = 0`` has NaN ``auroc``, ``ap``
+    and ``tpr``.  Replicates are processed ``chunk_elems // n`` at a time."""
+    pl = BootstrapPlan(y, score, stratified, threshold)
+    dev = score.device
+    n, G = pl.n, int(grid_points)
+    b1 = n_boot if b1 is None else b1
+    i64, f64 = torch.int64, torch.float64
+    ys = pl.y.to(i64)
+    rows = torch.arange(n, device=dev)
+    ends = torch.nonzero(pl.glast.to(i64) == rows).squeeze(1)          # last row of every tie group
+    f = pl.gfirst.to(i64)[ends]
+    prev = (f - 1).clamp(min=0)
+    E = ends.numel()
+    j = torch.arange(n, dtype=i64, device=dev)
+    head = j < pl.p0
+    m = torch.where(head, pl.p0, n - pl.p0)
+    off = torch.where(head, 0, pl.p0)
+    sd = torch.tensor(_seed_i64(seed), dtype=i64, device=dev)
+    g = torch.arange(G, dtype=i64, device=dev)
+    G1 = G - 1
+    nan = float("nan")
+    outs = [[] for _ in range(6)]
+    per = max(1, chunk_elems // n)
+    for c0 in range(b0, b1, per):
+        bs = torch.arange(c0, min(b1, c0 + per), dtype=i64, device=dev)
+        Bc = bs.numel()
+        u = _splitmix64_t(sd ^ _splitmix64_t((bs[:, None] << 40) ^ j[None, :]))
+        r = (((u >> 32) & 0xFFFFFFFF) * m[None, :]) >> 32
+        at = pl.map.to(i64)[off[None, :] + r] + torch.arange(Bc, device=dev)[:, None] * n
+        cnt = torch.bincount(at.reshape(-1), minlength=Bc * n).reshape(Bc, n)
+        cp = torch.cumsum(cnt * ys, 1)
+        cn = torch.cumsum(cnt * (1 - ys), 1)
+        Pb, Nb = cp[:, -1], cn[:, -1]
+        deg = (Pb == 0) | (Nb == 0)
+        TP, FP = cp[:, ends], cn[:, ends]
+        TP0 = torch.where(f > 0, cp[:, prev], 0)
+        FP0 = torch.where(f > 0, cn[:, prev], 0)
+        a2 = ((FP - FP0) * (TP + TP0)).sum(1)
+        auroc = a2.to(f64) / (2 * Pb * Nb).to(f64)
+        tot = TP + FP
+        term = torch.where(tot > 0, ((TP - TP0) * TP).to(f64) / tot.clamp(min=1).to(f64), 0.0)
+        ap = term.sum(1) / Pb.to(f64)
+        if pl.k0 > 0:
+            tpc, fpc = cp[:, pl.k0 - 1], cn[:, pl.k0 - 1]
+        else:
+            tpc, fpc = torch.zeros_like(Pb), torch.zeros_like(Pb)
+        conf = torch.stack([tpc, fpc, Pb - tpc, Nb - fpc], 1)
+        # ROC vertices: (0, 0), then the tie-group ends
+        z = torch.zeros(Bc, 1, dtype=i64, device=dev)
+        V, T = torch.cat([z, FP], 1), torch.cat([z, TP], 1)
+        bound = g[None, :] * Nb[:, None]
+        ks = torch.searchsorted((V * G1).contiguous(), bound.contiguous(), right=True) - 1
+        nx = (ks + 1).clamp(max=E)
+        vk, tk = torch.gather(V, 1, ks), torch.gather(T, 1, ks)
+        v1, t1 = torch.gather(V, 1, nx), torch.gather(T, 1, nx)
+        exact = (vk * G1 == bound) | (ks == E)
+        num = bound - vk * G1
+        den = torch.where(exact, 1, G1 * (v1 - vk))
+        frac = num.to(f64) / den.to(f64)
+        pbf = Pb.to(f64)[:, None]
+        tpr = torch.where(exact, tk.to(f64) / pbf, (tk.to(f64) + (t1 - tk).to(f64) * frac) / pbf)
+        auroc = torch.where(deg, nan, auroc)
+        ap = torch.where(deg, nan, ap)
+        tpr = torch.where(deg[:, None], nan, tpr)
+        for o, v in zip(outs, (auroc, ap, a2, torch.stack([Pb, Nb], 1), conf, tpr)):
+            o.append(v)
+    if not outs[0]:
+        e = torch.empty
+        return (e(0, dtype=f64, device=dev), e(0, dtype=f64, device=dev), e(0, dtype=i64, device=dev),
+                e(0, 2, dtype=i64, device=dev), e(0, 4, dtype=i64, device=dev), e(0, G, dtype=f64, device=dev))
+    return tuple(torch.cat(o) for o in outs)
+
+
+def _splitmix64_py(x: int) -> int:
+    M = (1 << 64) - 1
+    x = (x + 0x9E3779B97F4A7C15) & M
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M
+    return x ^ (x >> 31)
+
+
+def bootstrap_resample(y, b: int, seed: int = 0, stratified: bool = False):
+    """The original row indices replicate ``b`` draws, in draw order, by Python integers."""
+    y = [int(v) for v in y]
+    n = len(y)
+    sd = int(seed) & ((1 << 64) - 1)
+
+    def draw(j, m):
+        u = _splitmix64_py(sd ^ _splitmix64_py(((b << 40) & ((1 << 64) - 1)) ^ j))
+        return ((u >> 32) * m) >> 32
+    if not stratified:
+        return [draw(j, n) for j in range(n)]
+    pos = [i for i in range(n) if y[i] == 1]
+    neg = [i for i in range(n) if y[i] != 1]
+    return [pos[draw(j, len(pos))] for j in range(len(pos))] + [neg[draw(j, len(neg))] for j in range(len(pos), n)]
+
+
+def bootstrap_oracle(y, score, n_boot: int, *, seed: int = 0, stratified: bool = False,
+                     threshold: float = 0.5, grid_points: int = 101, b0: int = 0, b1=None):
+    """Independent oracle for the tests, O(n²) per replicate: the resampled rows are materialised
+    from a Python-integer splitmix64; AUROC counts (positive, negative) pairs, 2 for a win and 1
+    for a tie, and divides the exact integers as ``numpy.longdouble``; AP and the grid TPR follow
+    the textbook definitions on the materialised sample (AP = Σ ΔR·precision over the distinct
+    scores; TPR = the ROC polyline with a (0, 0) vertex, read at FPR = g/(G−1), the upper point of a
+    vertical run), in longdouble with the vertex comparisons in exact integers; the confusion
+    counts are counted.  Returns numpy arrays named as the op's outputs (``auroc``, ``ap``, ``tpr``
+    longdouble, the rest int64) in a dict, plus ``n_degenerate``."""
+    np = _np()
+    ld = np.longdouble
+    y = [int(v) for v in np.asarray(y).reshape(-1)]
+    s = [float(v) for v in np.asarray(score, dtype=np.float64).reshape(-1)]
+    G = int(grid_points)
+    b1 = n_boot if b1 is None else b1
+    out = {k: [] for k in ("auroc", "ap", "a2", "pn", "conf", "tpr")}
+    for b in range(b0, b1):
+        idx = bootstrap_resample(y, b, seed, stratified)
+        yy = [y[i] for i in idx]
+        sc = [s[i] for i in idx]
+        ps = [v for v, l in zip(sc, yy) if l == 1]
+        ns = [v for v, l in zip(sc, yy) if l != 1]
+        P, N = len(ps), len(ns)
+        a2 = sum(2 if p > q else (1 if p == q else 0) for p in ps for q in ns)
+        tp = sum(1 for v, l in zip(sc, yy) if v > threshold and l == 1)
+        fp = sum(1 for v, l in zip(sc, yy) if v > threshold and l != 1)
+        out["a2"].append(a2)
+        out["pn"].append([P, N])
+        out["conf"].append([tp, fp, P - tp, N - fp])
+        if P == 0 or N == 0:
+            out["auroc"].append(ld("nan"))
+            out["ap"].append(ld("nan"))
+            out["tpr"].append([ld("nan")] * G)
+            continue
+        out["auroc"].append(ld(a2) / ld(2 * P * N))
+        verts = [(0, 0)]                       # (FP, TP) at every distinct score, descending
+        ap = ld(0)
+        for v in sorted(set(sc), reverse=True):
+            t = sum(1 for q in ps if q >= v)
+            f_ = sum(1 for q in ns if q >= v)
+            ap += (ld(t) / ld(P) - ld(verts[-1][1]) / ld(P)) * (ld(t) / ld(t + f_))
+            verts.append((f_, t))
+        out["ap"].append(ap)
+        row = []
+        for gi in range(G):
+            k = max(i for i, (f_, _) in enumerate(verts) if f_ * (G - 1) <= gi * N)
+            fk, tk = verts[k]
+            if k == len(verts) - 1 or fk * (G - 1) == gi * N:
+                row.append(ld(tk) / ld(P))
+                continue
+            f1, t1 = verts[k + 1]
+            q = ld(gi) / ld(G - 1)
+            x0, x1 = ld(fk) / ld(N), ld(f1) / ld(N)
+            y0, y1 = ld(tk) / ld(P), ld(t1) / ld(P)
+            row.append(y0 + (y1 - y0) * (q - x0) / (x1 - x0))
+        out["tpr"].append(row)
+    res = {"auroc": np.array(out["auroc"], dtype=ld), "ap": np.array(out["ap"], dtype=ld),
+           "a2": np.array(out["a2"], dtype=np.int64), "pn": np.array(out["pn"], dtype=np.int64).reshape(-1, 2),
+           "conf": np.array(out["conf"], dtype=np.int64).reshape(-1, 4),
+           "tpr": np.array(out["tpr"], dtype=ld).reshape(-1, G)}
+    res["n_degenerate"] = int(np.isnan(res["auroc"]).sum())
+    return res

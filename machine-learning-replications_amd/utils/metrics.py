@@ -7,6 +7,8 @@
   ``roc_curve`` drops collinear points like sklearn's ``drop_intermediate=True``.
 * :func:`wald_band` — the reference's ``±1.96·sqrt(p(1−p)/n)`` band with ``n`` =
   total held-out rows (``train_ensemble_public.py:74-77,82-85``).
+* :func:`bootstrap_ci` — percentile intervals of AUROC, AP and the thresholded rates from the
+  nonparametric bootstrap of the held-out rows (``ops.bootstrap_metrics``), plus a ROC band.
 * :func:`save_plots` — headless PNGs of both figures (the reference calls
   ``plt.show()``; its PR axis labels are swapped, ``:86-87`` — kept here with a
   corrected label since the plot is re-drawn, not pixel-copied).
@@ -179,9 +181,70 @@ def evaluate(y_true, proba1) -> Dict[str, float]:
             "accuracy": (tp + tn) / max(1, tp + tn + fp + fn), "tp": tp, "fp": fp, "tn": tn, "fn": fn}
 
 
-def _svg_curve(path: str, x, y, lo, hi, xlabel: str, ylabel: str, label: str, diagonal: bool) -> str:
+def bootstrap_ci(y_true, proba1, n_boot: int = 2000, seed: int = 2020, alpha: float = 0.05,
+                 stratified: bool = False, threshold: float = 0.5, device=None) -> Dict[str, object]:
+    """Nonparametric bootstrap of the held-out rows: ``n_boot`` resamples with replacement
+    (``ops.bootstrap_metrics``: the fused kernel on a GPU, its torch mirror on the host;
+    ``device`` defaults to where ``proba1`` lives), everything recomputed on each.
+
+    For ``auroc``, ``average_precision`` and, at ``proba1 > threshold``, the class-1
+    ``precision`` and ``recall``, the ``specificity`` and the ``accuracy``, returns
+    ``{"point", "lo", "hi", "se"}``: the point estimate from this module's functions on the
+    original sample, the percentile interval bounds at ``alpha/2`` and ``1 − alpha/2`` (linear
+    interpolation) and the standard deviation of the replicates.  A degenerate replicate (no
+    positive or no negative row drawn; plain mode only) is counted in ``n_degenerate`` and left out
+    of every quantile, as is a replicate whose own ratio is 0/0.  ``fpr_grid`` and ``tpr_lo`` /
+    ``tpr_median`` / ``tpr_hi`` are the pointwise band of the replicates' ROC curves.  All values
+    are Python floats and lists."""
+    from .. import ops
+    y = _t(y_true).reshape(-1)
+    p = _t(proba1).reshape(-1)
+    dev = torch.device(device) if device is not None else p.device
+    y, p = y.to(dev), p.to(dev)
+    if not p.is_floating_point():
+        p = p.to(torch.float64)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"bootstrap_ci: alpha = {alpha} outside (0, 1)")
+    auroc, ap, _, pn, conf, tpr = ops.bootstrap_metrics(y, p, n_boot, seed=seed, stratified=stratified,
+                                                        threshold=threshold)
+    auroc, ap, tpr = auroc.cpu().numpy(), ap.cpu().numpy(), tpr.cpu().numpy()
+    pn, conf = pn.cpu().numpy(), conf.cpu().numpy().astype(np.float64)
+    deg = (pn[:, 0] == 0) | (pn[:, 1] == 0)
+    tp, fp, fn, tn = conf.T
+    with np.errstate(invalid="ignore", divide="ignore"):
+        reps = {"auroc": auroc, "average_precision": ap, "precision": tp / (tp + fp), "recall": tp / (tp + fn),
+                "specificity": tn / (tn + fp), "accuracy": (tp + tn) / (tp + fp + fn + tn)}
+    # point estimates on host copies: one sort, and the same digits whatever the device
+    yh, ph = y.cpu(), p.cpu()
+    tn0, fp0, fn0, tp0 = confusion(yh, (ph > threshold).to(torch.float64))
+
+    def ratio(a, b):
+        return a / b if b > 0 else float("nan")
+    point = {"auroc": roc_auc(yh, ph), "average_precision": average_precision(yh, ph),
+             "precision": ratio(tp0, tp0 + fp0), "recall": ratio(tp0, tp0 + fn0),
+             "specificity": ratio(tn0, tn0 + fp0), "accuracy": ratio(tp0 + tn0, tp0 + tn0 + fp0 + fn0)}
+    qs = [alpha / 2, 1 - alpha / 2]
+    out: Dict[str, object] = {"n_boot": int(n_boot), "seed": int(seed), "alpha": float(alpha),
+                              "stratified": bool(stratified), "threshold": float(threshold),
+                              "n_degenerate": int(deg.sum())}
+    for k, v in reps.items():
+        v = np.where(deg, np.nan, v)
+        ok = v[~np.isnan(v)]
+        lo, hi = (np.quantile(ok, qs) if ok.size else (float("nan"), float("nan")))
+        out[k] = {"point": float(point[k]), "lo": float(lo), "hi": float(hi),
+                  "se": float(np.std(ok, ddof=1)) if ok.size > 1 else float("nan")}
+    G = tpr.shape[1]
+    keep = tpr[~deg]
+    band = np.quantile(keep, [qs[0], 0.5, qs[1]], axis=0) if keep.shape[0] else np.full((3, G), np.nan)
+    out["fpr_grid"] = [g / (G - 1) for g in range(G)]
+    out["tpr_lo"], out["tpr_median"], out["tpr_hi"] = (band[i].tolist() for i in range(3))
+    return out
+
+
+def _svg_curve(path: str, x, y, lo, hi, xlabel: str, ylabel: str, label: str, diagonal: bool, band_x=None) -> str:
     """Minimal dependency-free SVG line plot with a shaded ±band (headless nodes without
-    matplotlib): same content as the reference figures (T:66-90)."""
+    matplotlib): same content as the reference figures (T:66-90).  ``band_x``: abscissae of
+    ``lo``/``hi`` when they are not the curve's."""
     W, H, m = 480, 400, 50
     def px(v):
         return m + float(v) * (W - 2 * m)
@@ -189,6 +252,8 @@ def _svg_curve(path: str, x, y, lo, hi, xlabel: str, ylabel: str, label: str, di
         return H - m - float(v) * (H - 2 * m)
     xs = [float(v) for v in x]
     pts = " ".join(f"{px(a):.2f},{py(b):.2f}" for a, b in zip(xs, y))
+    if band_x is not None:
+        xs = [float(v) for v in band_x]
     band = " ".join(f"{px(a):.2f},{py(min(1.0, max(0.0, float(b)))):.2f}" for a, b in zip(xs, hi))
     band += " " + " ".join(f"{px(a):.2f},{py(min(1.0, max(0.0, float(b)))):.2f}"
                            for a, b in zip(reversed(xs), reversed([float(v) for v in lo])))
@@ -209,9 +274,15 @@ def _svg_curve(path: str, x, y, lo, hi, xlabel: str, ylabel: str, label: str, di
     return path
 
 
-def save_plots(y_true, proba1, prefix: str) -> Optional[Tuple[str, str]]:
+def save_plots(y_true, proba1, prefix: str, band=None) -> Optional[Tuple[str, str]]:
     """ROC and PR figures with the Wald ±band (reference T:66-90; saved instead of shown).
-    PNG through matplotlib when it is installed, otherwise self-contained SVG."""
+    PNG through matplotlib when it is installed, otherwise self-contained SVG.  ``band`` =
+    ``(fpr_grid, tpr_lo, tpr_hi)`` from :func:`bootstrap_ci` is shaded on the ROC figure in place
+    of the Wald band; the PR figure keeps the Wald band (there is no bootstrap PR band)."""
+    if band is not None:
+        band = tuple(np.asarray(b, dtype=np.float64) for b in band)
+        if any(np.isnan(b).any() for b in band):
+            band = None     # every replicate degenerate: nothing to shade
     try:
         import matplotlib
         matplotlib.use("Agg")
@@ -221,9 +292,9 @@ def save_plots(y_true, proba1, prefix: str) -> Optional[Tuple[str, str]]:
         p = _t(proba1).cpu()
         n = y.numel()
         fpr, tpr, _ = roc_curve(y, p)
-        lo, hi = wald_band(tpr, n)
+        lo, hi = wald_band(tpr, n) if band is None else band[1:]
         roc = _svg_curve(prefix + "_roc.svg", fpr, tpr, lo, hi, "False Positive Rate", "True Positive Rate",
-                         f"ensemble (AUC = {auc(fpr, tpr):.2f})", True)
+                         f"ensemble (AUC = {auc(fpr, tpr):.2f})", True, band_x=None if band is None else band[0])
         prec, rec, _ = precision_recall_curve(y, p)
         lo, hi = wald_band(prec, n)
         pr = _svg_curve(prefix + "_pr.svg", rec, prec, lo, hi, "Recall", "Precision",
@@ -237,7 +308,10 @@ def save_plots(y_true, proba1, prefix: str) -> Optional[Tuple[str, str]]:
     fig = plt.figure()
     plt.plot(fpr.numpy(), tpr.numpy(), label=f"ensemble (AUC = {auc(fpr, tpr):.2f})")
     plt.plot([0, 1], [0, 1], "k--")
-    plt.fill_between(fpr.numpy(), lo.numpy(), hi.numpy(), color="grey", alpha=.2, label=r"$\pm$ 1 std. dev.")
+    if band is None:
+        plt.fill_between(fpr.numpy(), lo.numpy(), hi.numpy(), color="grey", alpha=.2, label=r"$\pm$ 1 std. dev.")
+    else:
+        plt.fill_between(band[0], band[1], band[2], color="grey", alpha=.2, label="bootstrap band")
     plt.xlim([0.0, 1.0]); plt.ylim([0.0, 1.0])
     plt.xlabel("False Positive Rate"); plt.ylabel("True Positive Rate"); plt.grid(True); plt.legend()
     roc_path = prefix + "_roc.png"
