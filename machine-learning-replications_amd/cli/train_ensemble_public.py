@@ -12,7 +12,9 @@ cohort is generated (``--rows``, ``--features``).  Extras: ``--device cuda``, ``
 (writes the sklearn-0.23.2 ``.pkl`` layout that ``predict_hf.py`` reads),
 ``--timings``, ``--bootstrap N`` (percentile confidence intervals of the held-out AUROC, AP
 and thresholded rates from N bootstrap resamples, and a bootstrap band on the ROC figure;
-``--bootstrap-seed``, ``--stratified``); under ``torchrun`` the development rows are sharded
+``--bootstrap-seed``, ``--stratified``), ``--calibration`` (Brier, O:E, calibration intercept and
+slope, ECE and net benefit of the held-out risks, a reliability and a decision-curve figure;
+intervals from the same resamples with ``--bootstrap N``); under ``torchrun`` the development rows are sharded
 over ranks.
 """
 from __future__ import annotations
@@ -46,6 +48,11 @@ def main(argv=None, script_dir=None) -> int:
     ap.add_argument("--bootstrap-seed", type=int, default=2020)
     ap.add_argument("--stratified", action="store_true",
                     help="resample positives and negatives separately (class totals fixed)")
+    ap.add_argument("--calibration", action="store_true",
+                    help="report Brier, O:E, calibration intercept/slope, ECE and net benefit of the held-out "
+                         "risks, with two figures; with --bootstrap N, their confidence intervals")
+    ap.add_argument("--calibration-bins", type=int, default=10)
+    ap.add_argument("--calibration-thresholds", type=int, default=99)
     a = ap.parse_args(argv)
     if a.bootstrap < 0:
         ap.error("--bootstrap must be >= 0")
@@ -88,7 +95,7 @@ def main(argv=None, script_dir=None) -> int:
     # are drawn from it, six times, in the stacking fit's order
     np.random.seed(cfg.seed)
     res = develop(X_dev, y_dev, X_sel, y_sel, names, device=device, group=group, cfg=cfg)
-    if a.plots or a.bootstrap:
+    if a.plots or a.bootstrap or a.calibration:
         # collectives on EVERY rank (before the rank-0 block); only rank 0 draws
         p_all = res.proba_sel
         y_all = torch.as_tensor(y_sel, device=p_all.device)
@@ -111,11 +118,33 @@ def main(argv=None, script_dir=None) -> int:
                 return f"{ci[k]['point']:.4f} ({lvl} {ci[k]['lo']:.4f}\u2013{ci[k]['hi']:.4f})"
             print(f"AUROC = {fmt('auroc')}   AP = {fmt('average_precision')}")
             print("   ".join(f"{k} = {fmt(k)}" for k in ("precision", "recall", "specificity", "accuracy")))
+        cal = None
+        if a.calibration:
+            cal = metrics.calibration_ci(y_all, p_all, n_boot=a.bootstrap, seed=a.bootstrap_seed,
+                                         stratified=a.stratified, bins=a.calibration_bins,
+                                         thresholds=a.calibration_thresholds)
+            lvl = f"{100 * (1 - cal['alpha']):g}% CI"
+
+            def cell(v, digits=4):
+                s = f"{v['point']:.{digits}f}"
+                return s + (f" ({lvl} {v['lo']:.{digits}f}–{v['hi']:.{digits}f})" if a.bootstrap else "")
+            print("   ".join(f"{name} = {cell(cal[k])}" for name, k in (
+                ("Brier", "brier"), ("O:E", "oe_ratio"), ("intercept", "intercept"), ("slope", "slope"),
+                ("ECE", "ece"))))
+            dcv = cal["decision_curve"]
+            at = []
+            for want in (0.1, 0.2, 0.5):
+                g = min(range(len(dcv["thresholds"])), key=lambda i: abs(dcv["thresholds"][i] - want))
+                nb = {"point": dcv["net_benefit"][g], "lo": dcv["net_benefit_lo"][g], "hi": dcv["net_benefit_hi"][g]}
+                at.append(f"t = {dcv['thresholds'][g]:.2f}: {cell(nb)} vs treat-all {dcv['net_benefit_all'][g]:.4f}")
+            print("net benefit   " + "   ".join(at))
         if a.timings:
             print(res.timer.table())
         if a.plots:
             band = (ci["fpr_grid"], ci["tpr_lo"], ci["tpr_hi"]) if ci else None
             print("plots:", metrics.save_plots(y_all, p_all, a.plots, band=band))
+            if cal is not None:
+                print("calibration plots:", metrics.save_calibration_plots(cal, a.plots))
         if a.save_model:
             from ..io.checkpoint import save_checkpoint
             model = res.model
@@ -128,6 +157,8 @@ def main(argv=None, script_dir=None) -> int:
                         "timings": dict(res.timer.times), "world_size": world}
                 if ci is not None:
                     line["bootstrap"] = ci
+                if cal is not None:
+                    line["calibration"] = cal
                 f.write(json.dumps(line) + "\n")
     pdist.shutdown()
     return 0

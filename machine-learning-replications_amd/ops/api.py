@@ -8,7 +8,8 @@ from . import reference as ref
 from .packing import pack_forest, pack_stack, pack_svs
 
 __all__ = ["rbf_decision", "svc_proba1", "tree_raw", "expit", "pack_svs", "pack_forest", "pack_stack",
-           "stack_infer", "stack_shapley", "weighted_moments", "bootstrap_metrics"]
+           "stack_infer", "stack_shapley", "weighted_moments", "bootstrap_metrics",
+           "bootstrap_calibration"]
 
 
 def _c(t: torch.Tensor, dtype) -> torch.Tensor:
@@ -251,6 +252,95 @@ def _bootstrap_device(y, score, *, seed, stratified, threshold, grid_points, b0,
                             a2.data_ptr(), pn.data_ptr(), conf.data_ptr(), tpr.data_ptr(), int(grid),
                             stream_ptr(dev))
     return auroc, ap, a2, pn, conf, tpr
+
+
+CALIBRATION_LDS_ROWS = 20000       # rows whose two u32 arrays fit beside the kernel's 2,176 B of scratch (csrc/calibration.hip)
+CALIBRATION_MAX_BINS = 64
+CALIBRATION_MAX_THRESHOLDS = 4096
+_CALIBRATION_FORCE_GLOBAL = False  # tests: take the global-workspace path below the LDS limit too
+
+
+def bootstrap_calibration(y, score, n_boot: int, *, seed: int = 0, stratified: bool = False, bins: int = 10,
+                          thresholds: int = 99, b0: int = 0, b1=None, grid: int = 0, stream=None):
+    """Bootstrap replicates ``b0:b1`` (default all ``n_boot``) of the calibration and decision-curve
+    statistics of binary labels ``y [n]`` and predicted risks ``score [n]`` in [0, 1] (f32 or f64).
+
+    The resamples are those of :func:`bootstrap_metrics` for the same ``seed``, mode and replicate.
+    Returns a :class:`reference.CalibrationBootstrap` (a tuple with named fields): ``pn [B, 2]``,
+    ``brier [B]`` = Σc(p−y)²/n, ``sum_p [B]`` = Σc·p, the reliability bins ``bin_n``, ``bin_pos``
+    (int64) and ``bin_sum_p`` (f64) ``[B, bins]`` (bin of p = #{k ∈ 1..bins−1 : p ≥ k/bins}),
+    ``dc [B, thresholds, 2]`` = TP and FP among the rows with p ≥ g/(thresholds+1), ``status [B]``
+    (0 fitted, 1 one class only, 2 classes separable: no MLE, 3 iteration cap), ``coef [B, 2]`` = the
+    intercept and slope of the count-weighted logistic fit of y on logit(p) (p clamped to
+    [1e-12, 1 − 1e-12]; NaN unless status 0) and its Newton step count ``iters [B]``.
+    ``stream``, if given, is a raw HIP stream handle: everything is enqueued on it."""
+    if y.dim() != 1 or score.dim() != 1 or y.numel() != score.numel():
+        raise ValueError(f"bootstrap_calibration: y {tuple(y.shape)} and score {tuple(score.shape)} must be "
+                         "1-D of one length")
+    n = score.numel()
+    if n == 0:
+        raise ValueError("bootstrap_calibration: y and score are empty (n = 0)")
+    if n > BOOTSTRAP_MAX_N:
+        raise ValueError(f"bootstrap_calibration: y has {n} rows, the limit is n <= {BOOTSTRAP_MAX_N}")
+    if y.device != score.device:
+        raise ValueError("bootstrap_calibration: y and score must be on the same device")
+    if not score.is_floating_point() or not bool(torch.isfinite(score).all()):
+        raise ValueError("bootstrap_calibration: score must be finite floating point")
+    if not bool(((score >= 0) & (score <= 1)).all()):
+        raise ValueError("bootstrap_calibration: score must lie in [0, 1]")
+    if not bool(((y == 0) | (y == 1)).all()):
+        raise ValueError("bootstrap_calibration: y must hold labels 0 and 1 only")
+    n_boot = int(n_boot)
+    if not 1 <= n_boot <= BOOTSTRAP_MAX_B:
+        raise ValueError(f"bootstrap_calibration: n_boot = {n_boot} outside 1..{BOOTSTRAP_MAX_B}")
+    b1 = n_boot if b1 is None else int(b1)
+    b0 = int(b0)
+    if not 0 <= b0 <= b1 <= n_boot:
+        raise ValueError(f"bootstrap_calibration: b0:b1 = {b0}:{b1} is not a range within 0..n_boot = {n_boot}")
+    K, T = int(bins), int(thresholds)
+    if not 1 <= K <= CALIBRATION_MAX_BINS:
+        raise ValueError(f"bootstrap_calibration: bins = {K} outside 1..{CALIBRATION_MAX_BINS}")
+    if not 1 <= T <= CALIBRATION_MAX_THRESHOLDS:
+        raise ValueError(f"bootstrap_calibration: thresholds = {T} outside 1..{CALIBRATION_MAX_THRESHOLDS}")
+    if stratified:
+        P = int((y == 1).sum())
+        if P == 0 or P == n:
+            raise ValueError("bootstrap_calibration: stratified resampling needs both classes in y")
+    kw = dict(seed=seed, stratified=bool(stratified), bins=K, thresholds=T, b0=b0, b1=b1)
+    if not score.is_cuda:
+        return ref.bootstrap_calibration(y, score, n_boot, **kw)
+    if stream is not None:
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=score.device)):
+            return _calibration_device(y, score, grid=grid, **kw)
+    return _calibration_device(y, score, grid=grid, **kw)
+
+
+def _calibration_device(y, score, *, seed, stratified, bins, thresholds, b0, b1, grid):
+    """Validated ``cuda`` inputs; everything is enqueued on torch's current stream."""
+    from . import ext, stream_ptr
+    dev = score.device
+    pl = ref.CalibrationPlan(y, score, stratified, bins, thresholds)
+    n, K, T, B = pl.n, bins, thresholds, b1 - b0
+    f64, i64 = torch.float64, torch.int64
+
+    def e(*shape, dtype):
+        return torch.empty(*shape, dtype=dtype, device=dev)
+    out = ref.CalibrationBootstrap(e(B, 2, dtype=i64), e(B, dtype=f64), e(B, dtype=f64), e(B, K, dtype=i64),
+                                   e(B, K, dtype=i64), e(B, K, dtype=f64), e(B, T, 2, dtype=i64), e(B, dtype=i64),
+                                   e(B, 2, dtype=f64), e(B, dtype=i64))
+    if B == 0:
+        return out
+    use_lds = n <= CALIBRATION_LDS_ROWS and not _CALIBRATION_FORCE_GLOBAL
+    ws, slices = None, 0
+    if not use_lds:
+        ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+        slices = max(1, min(B, 2 * ncu, BOOTSTRAP_WS_BYTES // (8 * n)))
+        ws = torch.empty(slices, 2 * n, dtype=torch.int32, device=dev)
+    ext().bootstrap_calibration(pl.y.data_ptr(), pl.map.data_ptr(), pl.p.data_ptr(), pl.l.data_ptr(),
+                                pl.bin_end.data_ptr(), pl.thr_prefix.data_ptr(), n, pl.p0, K, T,
+                                ref._seed_i64(seed), b0, B, int(use_lds), ws.data_ptr() if ws is not None else 0,
+                                slices, *(t.data_ptr() for t in out), int(grid), stream_ptr(dev))
+    return out
 
 
 def expit(x):

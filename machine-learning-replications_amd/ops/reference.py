@@ -766,3 +766,301 @@ def bootstrap_oracle(y, score, n_boot: int, *, seed: int = 0, stratified: bool =
            "tpr": np.array(out["tpr"], dtype=ld).reshape(-1, G)}
     res["n_degenerate"] = int(np.isnan(res["auroc"]).sum())
     return res
+
+
+# ---- bootstrap of the calibration and decision-curve statistics --------------------------------------
+# Same resampling law as above (csrc/calibration.hip draws what csrc/bootstrap.hip draws).  Definitions
+# shared by the kernel, this mirror and the oracle:
+#   bin of p     = #{k ∈ 1..K−1 : p ≥ k/K}, k/K the f64 quotient, compared in f64 (0.3 is in [0.3, 0.4));
+#   treated at t = p ≥ t, thresholds t_g = g/(T+1), g = 1..T, the f64 quotient;
+#   logit        l = log(p̃) − log1p(−p̃), p̃ = min(max(p, 1e-12), 1 − 1e-12);
+#   status       1 degenerate (P_b = 0 or N_b = 0), 2 no MLE (the drawn classes do not overlap in l:
+#                not both min_pos < max_neg and min_neg < max_pos), 3 iteration cap, else 0;
+#   the fit      Newton on the weighted log-likelihood of logit P(y=1) = a + b·l from a = log(P_b/N_b),
+#                b = 0; it stops, applying the full step, when the undamped step has |δa|, |δb| ≤ 1e-10;
+#                otherwise the step is halved while the deviance rises by more than 1e-12·|deviance|
+#                (at most 40 times); at most 50 steps.  Deviance term: log1p(exp(−|e|)) + max(e, 0) − y·e.
+
+CAL_CLAMP = 1e-12
+CAL_STEP_TOL = 1e-10
+CAL_RISE = 1e-12
+CAL_MAX_ITER = 50
+CAL_MAX_HALVE = 40
+
+
+class CalibrationBootstrap(tuple):
+    """The outputs of ``bootstrap_calibration`` in order, also by name."""
+    _fields = ("pn", "brier", "sum_p", "bin_n", "bin_pos", "bin_sum_p", "dc", "status", "coef", "iters")
+
+    def __new__(cls, *vals):
+        assert len(vals) == len(cls._fields)
+        return super().__new__(cls, vals)
+
+    def __getattr__(self, name):
+        try:
+            return self[self._fields.index(name)]
+        except ValueError:
+            raise AttributeError(name) from None
+
+
+class CalibrationPlan(BootstrapPlan):
+    """``BootstrapPlan`` plus, in the same descending stable order: the scores ``p`` and their
+    clamped logits ``l`` (f64), ``bin_end`` (int32 [K]: rows scoring ≥ k/K, ``bin_end[0] = n``, so bin
+    k is rows ``bin_end[k+1]:bin_end[k]``) and ``thr_prefix`` (int32 [T]: rows scoring ≥ g/(T+1))."""
+
+    def __init__(self, y: torch.Tensor, score: torch.Tensor, stratified: bool, bins: int, thresholds: int):
+        super().__init__(y, score, stratified, 0.5)
+        dev = score.device
+        f64 = torch.float64
+        n, K, T = self.n, int(bins), int(thresholds)
+        asc = torch.sort(score.to(f64)).values
+        self.p = asc.flip(0).contiguous()
+        pt = self.p.clamp(CAL_CLAMP, 1.0 - CAL_CLAMP)
+        self.l = (torch.log(pt) - torch.log1p(-pt)).contiguous()
+        self.K, self.T = K, T
+        # the quotients are formed on the host: a device may divide by multiplying with a reciprocal
+        edges = torch.tensor([k / K for k in range(K)], dtype=f64).to(dev)
+        self.thresholds = torch.tensor([g / (T + 1) for g in range(1, T + 1)], dtype=f64).to(dev)
+        # rows ≥ t = n − #{rows < t}
+        self.bin_end = (n - torch.searchsorted(asc, edges, right=False)).to(torch.int32).contiguous()
+        self.bin_end[0] = n
+        self.thr_prefix = (n - torch.searchsorted(asc, self.thresholds, right=False)).to(torch.int32).contiguous()
+
+
+def _cal_eval(C, yf, l, a, b):
+    """Deviance, gradient and Hessian sums of the count-weighted log-likelihood at ``(a, b)`` [m]."""
+    e = a[:, None] + b[:, None] * l[None, :]
+    z = torch.exp(-e.abs())
+    q = 1.0 / (1.0 + z)
+    zq = z * q
+    dev = (C * (torch.log1p(z) + e.clamp(min=0) - yf[None, :] * e)).sum(1)
+    wr = C * (yf[None, :] - torch.where(e >= 0, q, zq))
+    wv = C * (zq * q)
+    return torch.stack([dev, wr.sum(1), wr @ l, wv.sum(1), wv @ l, wv @ (l * l)])
+
+
+def _cal_newton(C, yf, l, Pb, Nb):
+    """The fit of the header on every row of the count matrix ``C [m, n]`` (f64) at once.  Returns
+    ``coef [m, 2]`` (NaN where the cap was hit), ``iters [m]`` and ``capped [m]`` (bool)."""
+    m = C.shape[0]
+    dev = C.device
+    a = torch.log(Pb / Nb)
+    b = torch.zeros_like(a)
+    iters = torch.zeros(m, dtype=torch.int64, device=dev)
+    done = torch.zeros(m, dtype=torch.bool, device=dev)
+    S = _cal_eval(C, yf, l, a, b) if m else torch.zeros(6, 0, dtype=torch.float64, device=dev)
+    act = torch.arange(m, device=dev)
+    for it in range(1, CAL_MAX_ITER + 1):
+        if act.numel() == 0:
+            break
+        d0, g0, g1, h00, h01, h11 = S[:, act]
+        det = h00 * h11 - h01 * h01
+        da = (h11 * g0 - h01 * g1) / det
+        db = (h00 * g1 - h01 * g0) / det
+        iters[act] = it
+        conv = (da.abs() <= CAL_STEP_TOL) & (db.abs() <= CAL_STEP_TOL)
+        ca = act[conv]
+        a[ca] = a[ca] + da[conv]
+        b[ca] = b[ca] + db[conv]
+        done[ca] = True
+        act, da, db, d0 = act[~conv], da[~conv], db[~conv], d0[~conv]
+        if act.numel() == 0:
+            break
+        t = torch.ones_like(da)
+        a1, b1 = a[act].clone(), b[act].clone()
+        Sn = torch.empty(6, act.numel(), dtype=torch.float64, device=dev)
+        pend = torch.arange(act.numel(), device=dev)
+        Ca = C[act] if act.numel() < m else C
+        for h in range(CAL_MAX_HALVE + 1):
+            a1[pend] = a[act[pend]] + t[pend] * da[pend]
+            b1[pend] = b[act[pend]] + t[pend] * db[pend]
+            Sn[:, pend] = _cal_eval(Ca[pend] if pend.numel() < Ca.shape[0] else Ca, yf, l, a1[pend], b1[pend])
+            if h == CAL_MAX_HALVE:
+                break
+            rise = Sn[0, pend] - d0[pend] > CAL_RISE * d0[pend].abs()
+            pend = pend[rise]
+            if pend.numel() == 0:
+                break
+            t[pend] = t[pend] * 0.5
+        a[act], b[act] = a1, b1
+        S[:, act] = Sn
+    coef = torch.stack([a, b], 1)
+    coef[~done] = float("nan")
+    return coef, iters, ~done
+
+
+def _cal_stats(pl: CalibrationPlan, cnt: torch.Tensor):
+    """The ten outputs for the rows of the count matrix ``cnt [m, n]`` (int64) over the plan's order."""
+    i64, f64 = torch.int64, torch.float64
+    dev = cnt.device
+    m, n, K = cnt.shape[0], pl.n, pl.K
+    ys = pl.y.to(i64)
+    yf = ys.to(f64)
+    cp = torch.cumsum(cnt * ys, 1)
+    cn = torch.cumsum(cnt * (1 - ys), 1)
+    Pb, Nb = cp[:, -1], cn[:, -1]
+    C = cnt.to(f64)
+    brier = (C * ((pl.p - yf) ** 2)[None, :]).sum(1) / n
+    sum_p = (C * pl.p[None, :]).sum(1)
+    z = torch.zeros(m, 1, dtype=i64, device=dev)
+    cpz, cnz = torch.cat([z, cp], 1), torch.cat([z, cn], 1)
+    be = pl.bin_end.to(i64)
+    bs = torch.cat([be[1:], torch.zeros(1, dtype=i64, device=dev)])
+    bin_pos = cpz[:, be] - cpz[:, bs]
+    bin_n = bin_pos + cnz[:, be] - cnz[:, bs]
+    bin_sum_p = torch.stack([(C[:, s:e] * pl.p[None, s:e]).sum(1) for s, e in zip(bs.tolist(), be.tolist())], 1)
+    th = pl.thr_prefix.to(i64)
+    dc = torch.stack([cpz[:, th], cnz[:, th]], 2)
+    # a class's largest l sits at its first drawn row of the descending order, its smallest at the last
+    rows = torch.arange(n, device=dev)
+    dpos, dneg = (cnt > 0) & (ys > 0)[None, :], (cnt > 0) & (ys == 0)[None, :]
+    fpos = torch.where(dpos, rows, n).min(1).values.clamp(max=n - 1)
+    lpos = torch.where(dpos, rows, -1).max(1).values.clamp(min=0)
+    fneg = torch.where(dneg, rows, n).min(1).values.clamp(max=n - 1)
+    lneg = torch.where(dneg, rows, -1).max(1).values.clamp(min=0)
+    deg = (Pb == 0) | (Nb == 0)
+    exists = (pl.l[lpos] < pl.l[fneg]) & (pl.l[lneg] < pl.l[fpos])
+    status = torch.where(deg, 1, torch.where(exists, 0, 2))
+    coef = torch.full((m, 2), float("nan"), dtype=f64, device=dev)
+    iters = torch.zeros(m, dtype=i64, device=dev)
+    fit = torch.nonzero(status == 0).squeeze(1)
+    if fit.numel():
+        c, it, capped = _cal_newton(C[fit] if fit.numel() < m else C, yf, pl.l, Pb[fit].to(f64), Nb[fit].to(f64))
+        coef[fit], iters[fit] = c, it
+        status[fit[capped]] = 3
+    return (torch.stack([Pb, Nb], 1), brier, sum_p, bin_n, bin_pos, bin_sum_p, dc, status, coef, iters)
+
+
+def bootstrap_calibration(y: torch.Tensor, score: torch.Tensor, n_boot: int, *, seed: int = 0,
+                          stratified: bool = False, bins: int = 10, thresholds: int = 99, b0: int = 0, b1=None,
+                          chunk_elems: int = 1 << 20):
+    """Vectorised torch mirror of the calibration kernel (and the host path of
+    ``ops.bootstrap_calibration``, which validates): the counts of ``bootstrap_metrics`` above, then
+    the kernel's formulas in int64 and f64 and its Newton rules on ``chunk_elems // n`` replicates at
+    a time.  Returns a :class:`CalibrationBootstrap` for replicates ``b0:b1``: ``pn [B, 2]``,
+    ``brier [B]``, ``sum_p [B]``, ``bin_n``/``bin_pos``/``bin_sum_p [B, K]``, ``dc [B, T, 2]`` (TP, FP),
+    ``status [B]``, ``coef [B, 2]`` (intercept, slope; NaN unless status 0) and ``iters [B]``."""
+    pl = CalibrationPlan(y, score, stratified, bins, thresholds)
+    dev = score.device
+    n, K, T = pl.n, pl.K, pl.T
+    b1 = n_boot if b1 is None else b1
+    i64, f64 = torch.int64, torch.float64
+    j = torch.arange(n, dtype=i64, device=dev)
+    head = j < pl.p0
+    m = torch.where(head, pl.p0, n - pl.p0)
+    off = torch.where(head, 0, pl.p0)
+    sd = torch.tensor(_seed_i64(seed), dtype=i64, device=dev)
+    outs = [[] for _ in range(10)]
+    per = max(1, chunk_elems // n)
+    for c0 in range(b0, b1, per):
+        bs = torch.arange(c0, min(b1, c0 + per), dtype=i64, device=dev)
+        Bc = bs.numel()
+        u = _splitmix64_t(sd ^ _splitmix64_t((bs[:, None] << 40) ^ j[None, :]))
+        r = (((u >> 32) & 0xFFFFFFFF) * m[None, :]) >> 32
+        at = pl.map.to(i64)[off[None, :] + r] + torch.arange(Bc, device=dev)[:, None] * n
+        cnt = torch.bincount(at.reshape(-1), minlength=Bc * n).reshape(Bc, n)
+        for o, v in zip(outs, _cal_stats(pl, cnt)):
+            o.append(v)
+    if not outs[0]:
+        def e(*shape, dtype):
+            return torch.empty(*shape, dtype=dtype, device=dev)
+        return CalibrationBootstrap(e(0, 2, dtype=i64), e(0, dtype=f64), e(0, dtype=f64), e(0, K, dtype=i64),
+                                    e(0, K, dtype=i64), e(0, K, dtype=f64), e(0, T, 2, dtype=i64), e(0, dtype=i64),
+                                    e(0, 2, dtype=f64), e(0, dtype=i64))
+    return CalibrationBootstrap(*(torch.cat(o) for o in outs))
+
+
+def calibration_point(y, p, bins: int = 10, thresholds: int = 99):
+    """The statistics of ``bootstrap_calibration`` on the original sample (every count 1), on the host:
+    a dict of Python numbers and lists named as the op's outputs, plus ``thresholds`` (the t_g)."""
+    y = torch.as_tensor(_np().asarray(y) if not isinstance(y, torch.Tensor) else y).reshape(-1).cpu()
+    p = torch.as_tensor(_np().asarray(p) if not isinstance(p, torch.Tensor) else p).reshape(-1).cpu().to(torch.float64)
+    pl = CalibrationPlan(y, p, False, bins, thresholds)
+    vals = _cal_stats(pl, torch.ones(1, pl.n, dtype=torch.int64))
+    out = {k: v[0].tolist() for k, v in zip(CalibrationBootstrap._fields, vals)}
+    out["thresholds"] = pl.thresholds.tolist()
+    return out
+
+
+def calibration_oracle(y, score, n_boot: int, *, seed: int = 0, stratified: bool = False, bins: int = 10,
+                       thresholds: int = 99, b0: int = 0, b1=None):
+    """Independent oracle for the tests, one replicate at a time on the rows materialised by
+    ``bootstrap_resample``: bins and treated rows are counted by comparing every drawn score with
+    k/K and g/(T+1); Brier and the sums are ``numpy.longdouble``; separability is decided on the
+    drawn (clamped) scores themselves; the fit is a longdouble Newton on the materialised rows, run
+    until the undamped step is below 1e-16·max(1, |a|, |b|).  Returns numpy arrays named as the
+    op's outputs (``brier``, ``sum_p``, ``bin_sum_p``, ``coef`` longdouble, the rest int64) in a dict."""
+    np = _np()
+    ld = np.longdouble
+    y = [int(v) for v in np.asarray(y).reshape(-1)]
+    s = [float(v) for v in np.asarray(score, dtype=np.float64).reshape(-1)]
+    n, K, T = len(y), int(bins), int(thresholds)
+    b1 = n_boot if b1 is None else b1
+    out = {k: [] for k in CalibrationBootstrap._fields}
+    for b in range(b0, b1):
+        idx = bootstrap_resample(y, b, seed, stratified)
+        yy = [y[i] for i in idx]
+        pp = [s[i] for i in idx]
+        P = sum(yy)
+        N = n - P
+        out["pn"].append([P, N])
+        out["brier"].append(sum(((ld(p) - ld(l)) ** 2 for p, l in zip(pp, yy)), ld(0)) / ld(n))
+        out["sum_p"].append(sum((ld(p) for p in pp), ld(0)))
+        bn, bp, bsum = [0] * K, [0] * K, [ld(0)] * K
+        for p, l in zip(pp, yy):
+            k = sum(1 for e in range(1, K) if p >= e / K)
+            bn[k] += 1
+            bp[k] += l
+            bsum[k] += ld(p)
+        out["bin_n"].append(bn)
+        out["bin_pos"].append(bp)
+        out["bin_sum_p"].append(bsum)
+        out["dc"].append([[sum(1 for p, l in zip(pp, yy) if p >= g / (T + 1) and l == 1),
+                           sum(1 for p, l in zip(pp, yy) if p >= g / (T + 1) and l != 1)] for g in range(1, T + 1)])
+        pc = [min(max(p, CAL_CLAMP), 1.0 - CAL_CLAMP) for p in pp]
+        ps = [v for v, l in zip(pc, yy) if l == 1]
+        ns = [v for v, l in zip(pc, yy) if l != 1]
+        nan2 = [ld("nan"), ld("nan")]
+        if P == 0 or N == 0:
+            st, cf, it = 1, nan2, 0
+        elif not (min(ps) < max(ns) and min(ns) < max(ps)):
+            st, cf, it = 2, nan2, 0
+        else:
+            x = np.array(pc, dtype=ld)
+            x = np.log(x) - np.log1p(-x)
+            t = np.array(yy, dtype=ld)
+
+            def deviance(a_, b_):
+                e = a_ + b_ * x
+                return np.sum(np.log1p(np.exp(-np.abs(e))) + np.maximum(e, 0) - t * e)
+            a_, b_ = np.log(ld(P) / ld(N)), ld(0)
+            st, cf, it = 3, nan2, 0
+            d_old = deviance(a_, b_)
+            for it in range(1, 201):
+                mu = 1 / (1 + np.exp(-(a_ + b_ * x)))
+                w = mu * (1 - mu)
+                g0, g1 = np.sum(t - mu), np.sum((t - mu) * x)
+                h00, h01, h11 = np.sum(w), np.sum(w * x), np.sum(w * x * x)
+                det = h00 * h11 - h01 * h01
+                da, db = (h11 * g0 - h01 * g1) / det, (h00 * g1 - h01 * g0) / det
+                if max(abs(da), abs(db)) <= ld(1e-16) * max(1, abs(a_), abs(b_)):
+                    st, cf = 0, [a_ + da, b_ + db]
+                    break
+                step = ld(1)
+                for _ in range(60):
+                    d_new = deviance(a_ + step * da, b_ + step * db)
+                    if not d_new - d_old > ld(1e-17) * abs(d_old):
+                        break
+                    step = step / 2
+                a_, b_, d_old = a_ + step * da, b_ + step * db, d_new
+        out["status"].append(st)
+        out["coef"].append(cf)
+        out["iters"].append(it)
+    B = b1 - b0
+    return {"pn": np.array(out["pn"], dtype=np.int64).reshape(B, 2), "brier": np.array(out["brier"], dtype=ld),
+            "sum_p": np.array(out["sum_p"], dtype=ld), "bin_n": np.array(out["bin_n"], dtype=np.int64).reshape(B, K),
+            "bin_pos": np.array(out["bin_pos"], dtype=np.int64).reshape(B, K),
+            "bin_sum_p": np.array(out["bin_sum_p"], dtype=ld).reshape(B, K),
+            "dc": np.array(out["dc"], dtype=np.int64).reshape(B, T, 2),
+            "status": np.array(out["status"], dtype=np.int64), "coef": np.array(out["coef"], dtype=ld).reshape(B, 2),
+            "iters": np.array(out["iters"], dtype=np.int64)}

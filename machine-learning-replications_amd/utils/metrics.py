@@ -9,6 +9,9 @@
   total held-out rows (``train_ensemble_public.py:74-77,82-85``).
 * :func:`bootstrap_ci` — percentile intervals of AUROC, AP and the thresholded rates from the
   nonparametric bootstrap of the held-out rows (``ops.bootstrap_metrics``), plus a ROC band.
+* :func:`calibration_ci` / :func:`save_calibration_plots` — Brier, O:E, calibration intercept and
+  slope, ECE, the reliability curve and the decision curve with bootstrap intervals
+  (``ops.bootstrap_calibration``, the same resamples), and their two figures.
 * :func:`save_plots` — headless PNGs of both figures (the reference calls
   ``plt.show()``; its PR axis labels are swapped, ``:86-87`` — kept here with a
   corrected label since the plot is re-drawn, not pixel-copied).
@@ -239,6 +242,180 @@ def bootstrap_ci(y_true, proba1, n_boot: int = 2000, seed: int = 2020, alpha: fl
     out["fpr_grid"] = [g / (G - 1) for g in range(G)]
     out["tpr_lo"], out["tpr_median"], out["tpr_hi"] = (band[i].tolist() for i in range(3))
     return out
+
+
+def calibration_ci(y_true, proba1, n_boot: int = 2000, seed: int = 2020, alpha: float = 0.05,
+                   stratified: bool = False, bins: int = 10, thresholds: int = 99, device=None) -> Dict[str, object]:
+    """Calibration and clinical usefulness of predicted risks with bootstrap intervals
+    (``ops.bootstrap_calibration``: the fused kernel on a GPU, its torch mirror on the host, on the
+    resamples :func:`bootstrap_ci` uses for the same ``seed`` and ``stratified``).
+
+    ``brier``, ``oe_ratio`` (observed positives / Σp), ``intercept`` and ``slope`` (logistic fit of y on
+    logit p: 0 and 1 when calibrated) and ``ece`` (Σ_k (n_k/n)·|observed rate − mean p| over the
+    non-empty uniform bins) are ``{"point", "lo", "hi", "se"}`` with the percentile rules of
+    :func:`bootstrap_ci`; the point estimates are ``reference.calibration_point`` on the original
+    sample.  ``reliability`` holds per bin ``pred_mean``, ``obs``, ``obs_lo``, ``obs_hi`` and ``count``
+    (replicates where the bin is empty are left out of its quantiles); ``decision_curve`` holds
+    ``thresholds`` t, ``net_benefit`` = TP/n − (FP/n)·t/(1−t) treating p ≥ t, with ``net_benefit_lo`` /
+    ``_hi``, and ``net_benefit_all`` (treat everyone).  Replicates without a fit are counted in
+    ``n_degenerate`` (one class drawn), ``n_separable`` (no MLE) and ``n_unconverged`` and left out of
+    the slope and intercept quantiles only.  ``n_boot = 0`` gives the points with NaN bounds."""
+    from .. import ops
+    from ..ops import reference as ref
+    y = _t(y_true).reshape(-1)
+    p = _t(proba1).reshape(-1)
+    dev = torch.device(device) if device is not None else p.device
+    y, p = y.to(dev), p.to(dev)
+    if not p.is_floating_point():
+        p = p.to(torch.float64)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"calibration_ci: alpha = {alpha} outside (0, 1)")
+    n_boot = int(n_boot)
+    if n_boot < 0:
+        raise ValueError(f"calibration_ci: n_boot = {n_boot} is negative")
+    # n_boot = 0: the empty range of one replicate, so the inputs are validated all the same
+    r = ops.bootstrap_calibration(y, p, max(n_boot, 1), seed=seed, stratified=stratified, bins=bins,
+                                  thresholds=thresholds, b1=None if n_boot else 0)
+    r = {k: v.cpu().numpy() for k, v in zip(ref.CalibrationBootstrap._fields, r)}
+    pt = ref.calibration_point(y.cpu(), p.cpu(), bins, thresholds)
+    n = int(y.numel())
+    t = np.asarray(pt["thresholds"], dtype=np.float64)
+    odds = t / (1.0 - t)
+
+    def derive(d):
+        pn, bn = np.asarray(d["pn"], dtype=np.float64), np.asarray(d["bin_n"], dtype=np.float64)
+        bp, bs = np.asarray(d["bin_pos"], dtype=np.float64), np.asarray(d["bin_sum_p"], dtype=np.float64)
+        dc, coef = np.asarray(d["dc"], dtype=np.float64), np.asarray(d["coef"], dtype=np.float64)
+        sp = np.asarray(d["sum_p"], dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            obs, pred = bp / bn, bs / bn
+            ece = np.where(bn > 0, (bn / n) * np.abs(obs - pred), 0.0).sum(-1)
+            oe = np.where(sp > 0, pn[..., 0] / sp, np.nan)
+        return {"brier": np.asarray(d["brier"], dtype=np.float64), "oe_ratio": oe, "intercept": coef[..., 0],
+                "slope": coef[..., 1], "ece": ece, "obs": obs, "pred": pred,
+                "nb": dc[..., 0] / n - (dc[..., 1] / n) * odds}
+    point, reps = derive(pt), derive(r)
+    qs = [alpha / 2, 1 - alpha / 2]
+    nan = float("nan")
+
+    def bounds(v):
+        ok = v[~np.isnan(v)]
+        lo, hi = np.quantile(ok, qs) if ok.size else (nan, nan)
+        return float(lo), float(hi), float(np.std(ok, ddof=1)) if ok.size > 1 else nan
+    out: Dict[str, object] = {"n_boot": n_boot, "seed": int(seed), "alpha": float(alpha),
+                              "stratified": bool(stratified), "bins": int(bins),
+                              "n_degenerate": int((r["status"] == 1).sum()),
+                              "n_separable": int((r["status"] == 2).sum()),
+                              "n_unconverged": int((r["status"] == 3).sum())}
+    for k in ("brier", "oe_ratio", "intercept", "slope", "ece"):
+        lo, hi, se = bounds(reps[k])
+        out[k] = {"point": float(point[k]), "lo": lo, "hi": hi, "se": se}
+    ob = [bounds(reps["obs"][:, k]) for k in range(int(bins))]
+    out["reliability"] = {"pred_mean": [float(v) for v in point["pred"]], "obs": [float(v) for v in point["obs"]],
+                          "obs_lo": [b[0] for b in ob], "obs_hi": [b[1] for b in ob],
+                          "count": [int(v) for v in pt["bin_n"]]}
+    nbq = [bounds(reps["nb"][:, g]) for g in range(t.size)]
+    P0, N0 = pt["pn"]
+    out["decision_curve"] = {"thresholds": t.tolist(), "net_benefit": point["nb"].tolist(),
+                             "net_benefit_lo": [b[0] for b in nbq], "net_benefit_hi": [b[1] for b in nbq],
+                             "net_benefit_all": (P0 / n - (N0 / n) * odds).tolist()}
+    return out
+
+
+def _svg_plot(path: str, curves, band, points, xlabel: str, ylabel: str, ylim) -> str:
+    """The approach of :func:`_svg_curve` for several curves on a y-range that need not be [0, 1]:
+    ``curves`` = ``(x, y, colour, dash, label)``, ``band`` = ``(x, lo, hi)`` or None, ``points`` =
+    ``(x, y)`` markers or None.  NaN vertices are skipped and values are clipped to ``ylim``."""
+    W, H, m = 480, 400, 50
+    y0, y1 = ylim
+
+    def px(v):
+        return m + float(v) * (W - 2 * m)
+
+    def py(v):
+        return H - m - (min(y1, max(y0, float(v))) - y0) / (y1 - y0) * (H - 2 * m)
+
+    def pts(xs, ys):
+        return " ".join(f"{px(a):.2f},{py(b):.2f}" for a, b in zip(xs, ys) if not (math.isnan(a) or math.isnan(b)))
+    parts = [f'<svg xmlns="http://www.w3.org/2000/svg" width="{W}" height="{H}" font-family="sans-serif" font-size="12">',
+             f'<rect x="{m}" y="{m}" width="{W - 2 * m}" height="{H - 2 * m}" fill="none" stroke="black"/>']
+    if band is not None:
+        keep = [(a, b, c) for a, b, c in zip(*band) if not (math.isnan(a) or math.isnan(b) or math.isnan(c))]
+        if keep:
+            poly = pts([k[0] for k in keep], [k[2] for k in keep]) + " " + \
+                pts([k[0] for k in reversed(keep)], [k[1] for k in reversed(keep)])
+            parts.append(f'<polygon points="{poly}" fill="grey" fill-opacity="0.2"/>')
+    for i, (x, y, colour, dash, label) in enumerate(curves):
+        d = f' stroke-dasharray="{dash}"' if dash else ""
+        parts.append(f'<polyline points="{pts(x, y)}" fill="none" stroke="{colour}" stroke-width="2"{d}/>')
+        parts.append(f'<text x="{m + 10}" y="{m + 18 + 14 * i}" fill="{colour}">{label}</text>')
+    if points is not None:
+        for a, b in zip(*points):
+            if not (math.isnan(a) or math.isnan(b)):
+                parts.append(f'<circle cx="{px(a):.2f}" cy="{py(b):.2f}" r="3" fill="#1f77b4"/>')
+    for k in range(5):
+        parts.append(f'<text x="{px(k / 4) - 8:.1f}" y="{H - m + 16}">{k / 4:g}</text>')
+        v = y0 + (y1 - y0) * k / 4
+        parts.append(f'<text x="{m - 40}" y="{py(v) + 4:.1f}">{v:.3g}</text>')
+    parts += [f'<text x="{W / 2 - 50}" y="{H - 12}">{xlabel}</text>',
+              f'<text x="12" y="{H / 2}" transform="rotate(-90 12 {H / 2})">{ylabel}</text>', "</svg>"]
+    with open(path, "w") as f:
+        f.write("\n".join(parts) + "\n")
+    return path
+
+
+def save_calibration_plots(result, prefix: str) -> Tuple[str, str]:
+    """The reliability diagram (``<prefix>_calibration``: the diagonal, the bins' observed rate
+    against their mean prediction, the bootstrap band of the observed rate) and the decision curve
+    (``<prefix>_decision``: the model, treat-all, treat-none and the model's band) of a
+    :func:`calibration_ci` result.  PNG through matplotlib when it is installed, otherwise SVG."""
+    rel, dcv = result["reliability"], result["decision_curve"]
+    keep = [k for k, c in enumerate(rel["count"]) if c > 0]
+    px_, obs = [rel["pred_mean"][k] for k in keep], [rel["obs"][k] for k in keep]
+    lo, hi = [rel["obs_lo"][k] for k in keep], [rel["obs_hi"][k] for k in keep]
+    has_band = not any(math.isnan(v) for v in lo + hi)
+    t, nb, nb_all = dcv["thresholds"], dcv["net_benefit"], dcv["net_benefit_all"]
+    nlo, nhi = dcv["net_benefit_lo"], dcv["net_benefit_hi"]
+    has_nband = not any(math.isnan(v) for v in nlo + nhi)
+    top = max([v for v in nb + nb_all + (nhi if has_nband else []) if not math.isnan(v)] + [0.01])
+    ylim = (-0.2 * top, 1.05 * top)     # treat-all dives far below zero: it is clipped there
+    label = f"ensemble (slope = {result['slope']['point']:.2f}, Brier = {result['brier']['point']:.3f})"
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except Exception:
+        cal = _svg_plot(prefix + "_calibration.svg",
+                        [([0.0, 1.0], [0.0, 1.0], "black", "5,4", "ideal"), (px_, obs, "#1f77b4", "", label)],
+                        (px_, lo, hi) if has_band else None, (px_, obs), "Mean predicted risk", "Observed rate",
+                        (0.0, 1.0))
+        dec = _svg_plot(prefix + "_decision.svg",
+                        [(t, nb, "#1f77b4", "", "ensemble"), (t, nb_all, "#d62728", "5,4", "treat all"),
+                         ([0.0, 1.0], [0.0, 0.0], "black", "2,3", "treat none")],
+                        (t, nlo, nhi) if has_nband else None, None, "Threshold probability", "Net benefit", ylim)
+        return cal, dec
+    fig = plt.figure()
+    plt.plot([0, 1], [0, 1], "k--", label="ideal")
+    plt.plot(px_, obs, "o-", label=label)
+    if has_band:
+        plt.fill_between(px_, lo, hi, color="grey", alpha=.2, label="bootstrap band")
+    plt.xlim([0.0, 1.0]); plt.ylim([0.0, 1.0])
+    plt.xlabel("Mean predicted risk"); plt.ylabel("Observed rate"); plt.grid(True); plt.legend()
+    cal = prefix + "_calibration.png"
+    fig.savefig(cal, dpi=120)
+    plt.close(fig)
+    fig = plt.figure()
+    plt.plot(t, nb, label="ensemble")
+    plt.plot(t, nb_all, "r--", label="treat all")
+    plt.plot([0, 1], [0, 0], "k:", label="treat none")
+    if has_nband:
+        plt.fill_between(t, nlo, nhi, color="grey", alpha=.2, label="bootstrap band")
+    plt.xlim([0.0, 1.0]); plt.ylim(list(ylim))
+    plt.xlabel("Threshold probability"); plt.ylabel("Net benefit"); plt.grid(True); plt.legend()
+    dec = prefix + "_decision.png"
+    fig.savefig(dec, dpi=120)
+    plt.close(fig)
+    return cal, dec
 
 
 def _svg_curve(path: str, x, y, lo, hi, xlabel: str, ylabel: str, label: str, diagonal: bool, band_x=None) -> str:
