@@ -230,9 +230,11 @@ constexpr size_t ws_sel_lds_bytes(int Q) { return 32 * 4 + 4096 * 4 + 1024 * 4 +
 // w·64M + m·64 + L: loads are coalesced and index order = (wave, m, lane), so ballots give
 // index-ordered ranks.
 //
-// ws_pick_lists: the k_up largest non-zero I_up keys, then the k_low largest I_low keys among the
-// positions not picked for I_up (two-level 11-bit radix histograms in LDS, ties taken in position
-// order: deterministic).  emit(i, p) is called for every pick (i = output slot, new picks of the up
+// ws_pick_lists: the k_up largest non-zero I_up keys, then the k_low largest I_low keys without the
+// positions picked for I_up (the low threshold is found over every I_low member and the up picks
+// are left out, not replaced: the low list may be shorter than k_low; two-level 11-bit radix
+// histograms in LDS, so keys are ranked by their top 22 bits, ties taken in position order:
+// deterministic; reference.ws_select_oracle).  emit(i, p) is called for every pick (i = output slot, new picks of the up
 // list first, each list in position order); returns the pick count.  Every thread calls it.
 template <int M, typename Emit>
 __device__ __forceinline__ int ws_pick_lists(const unsigned (&ku)[M], const unsigned (&kl)[M], int t0, int k_up,
@@ -778,6 +780,9 @@ __global__ __launch_bounds__(TH) void ws_solve_kernel(
     if (valid[m] && a[m] != (float)a0[m]) {
       const double C = pos[m] ? P.Cp : P.Cn;
       anew = a[m] <= 0.f ? 0.0 : (a[m] >= Cw[m] ? C : a0[m] + ((double)a[m] - (double)(float)a0[m]));
+      // (float)a0 may lie above a0 (or (float)C above C) by half an f32 ulp: an f32 α within that
+      // of a bound would leave the f64 box (tests/test_svm_ws_reference.py)
+      anew = fmin(fmax(anew, 0.0), C);
     }
     const bool ch = valid[m] && anew != a0[m];
     const unsigned long long cm = __ballot(ch);
@@ -1086,6 +1091,9 @@ __global__ __launch_bounds__(kWsThreads) void ws_kc_round_kernel(
     if (valid[m] && a[m] != (float)a0[m]) {
       const double C = pos[m] ? P.Cp : P.Cn;
       anew = a[m] <= 0.f ? 0.0 : (a[m] >= Cw[m] ? C : a0[m] + ((double)a[m] - (double)(float)a0[m]));
+      // (float)a0 may lie above a0 (or (float)C above C) by half an f32 ulp: an f32 α within that
+      // of a bound would leave the f64 box (tests/test_svm_ws_reference.py)
+      anew = fmin(fmax(anew, 0.0), C);
     }
     const bool ch = valid[m] && anew != a0[m];
     const unsigned long long cm = __ballot(ch);

@@ -1064,3 +1064,263 @@ def calibration_oracle(y, score, n_boot: int, *, seed: int = 0, stratified: bool
             "dc": np.array(out["dc"], dtype=np.int64).reshape(B, T, 2),
             "status": np.array(out["status"], dtype=np.int64), "coef": np.array(out["coef"], dtype=ld).reshape(B, 2),
             "iters": np.array(out["iters"], dtype=np.int64)}
+
+
+# ----------------------------------------------------------------------------- working-set SVC oracle
+# numpy only, written from libsvm's published rules (Fan, Chen, Lin 2005: the C-SVC dual, I_up / I_low,
+# m(α) − M(α), calculate_rho) and from the documented behaviour of ops/csrc/svm_ws.hip.  Nothing here
+# imports torch or models/smo.py, so a wrong sign, membership test or rounding in the solver is on one
+# side of the comparison only.  Conventions of the solver's problem table (``WsProb``): the first
+# ``npos`` points have y = +1, the rest y = −1; the box is [0, Cp] / [0, Cn]; the kernel is
+# K(a, b) = 2^(ngl2e·‖a − b‖²) with ``ngl2e`` = −γ·log2 e AS STORED, an f32.  That f32 defines γ
+# (γ = −ngl2e / log2 e exactly): quantising γ is part of the problem, not an arithmetic error.
+WS_LONGDOUBLE_MAX = 4096        # points up to which the oracle runs in longdouble
+
+
+def _ws_labels(l, npos, Cp, Cn):
+    np = _np()
+    pos = np.arange(l) < int(npos)
+    return pos, np.where(pos, 1.0, -1.0), np.where(pos, float(Cp), float(Cn))
+
+
+def ws_kernel_matvec(Z32, e2, v, dtype=None, rows=None):
+    """``Σ_c 2^(e2·‖z_t − z_c‖²)·v_c`` for every row t (or ``rows``), distances by direct differences,
+    over the columns with v_c ≠ 0 only (a zero column contributes an exact zero).  ``e2`` is the
+    base-2 exponent scale (−γ·log2 e), taken as given.  ``dtype`` longdouble, or float64 in row
+    chunks (see :func:`svc_dual_oracle`)."""
+    np = _np()
+    T = np.longdouble if dtype is None else dtype
+    Z = np.asarray(Z32, dtype=np.float32).astype(T)
+    v = np.asarray(v).astype(T)
+    cols = np.flatnonzero(v != 0)
+    R = Z if rows is None else Z[rows]
+    out = np.zeros(R.shape[0], dtype=T)
+    if cols.size == 0:
+        return out
+    B, vb = Z[cols], v[cols]
+    step = max(1, (1 << 21) // max(1, B.shape[0] * Z.shape[1]))
+    e2 = T(e2)
+    with np.errstate(under="ignore"):
+        for s in range(0, R.shape[0], step):
+            diff = R[s:s + step, None, :] - B[None, :, :]
+            d2 = (diff * diff).sum(-1)
+            out[s:s + step] = (np.exp2(e2 * d2) * vb[None, :]).sum(-1)
+    return out
+
+
+def svc_kkt(alpha, G, npos, Cp, Cn):
+    """libsvm's optimality measure and threshold from α and a gradient G (any float type):
+
+    * I_up = {y = +1, α < C} ∪ {y = −1, α > 0},  I_low = {y = +1, α > 0} ∪ {y = −1, α < C};
+      ``m = max_{I_up} −yG``, ``M = min_{I_low} −yG``; libsvm stops when m − M < eps.  Returned as
+      ``(gap, gmax_up, gmax_low)`` with gmax_up = m, gmax_low = −M, gap = gmax_up + gmax_low
+      (−inf for an empty set).
+    * ``calculate_rho``: the mean of yG over the free points (0 < α < C); with none,
+      (ub + lb)/2 where ub = min yG over {α = C, y = −1} ∪ {α = 0, y = +1} and lb = max yG over
+      {α = C, y = +1} ∪ {α = 0, y = −1}."""
+    np = _np()
+    alpha = np.asarray(alpha)
+    G = np.asarray(G)
+    pos, y, C = _ws_labels(alpha.shape[0], npos, Cp, Cn)
+    yG = np.where(pos, G, -G)
+    up = np.where(pos, alpha < C, alpha > 0)
+    low = np.where(pos, alpha > 0, alpha < C)
+    ninf = -np.inf
+    gu = (-yG[up]).max() if up.any() else ninf
+    gl = yG[low].max() if low.any() else ninf
+    upper, lower = alpha >= C, alpha <= 0
+    free = ~upper & ~lower
+    if free.any():
+        rho = yG[free].sum() / free.sum()
+    else:
+        ubm = (upper & ~pos) | (lower & ~upper & pos)
+        lbm = (upper & pos) | (lower & ~upper & ~pos)
+        ub = yG[ubm].min() if ubm.any() else np.inf
+        lb = yG[lbm].max() if lbm.any() else ninf
+        rho = (ub + lb) / 2
+    return {"gap": gu + gl, "gmax_up": gu, "gmax_low": gl, "rho": rho}
+
+
+def svc_dual_oracle(Z32, npos, Cp, Cn, ngl2e_f32, alpha):
+    """The C-SVC dual at ``alpha`` for the f32 rows ``Z32`` as the solver sees them.
+
+    Dual: min ½ αᵀQα − Σα, Q_tc = y_t y_c K_tc, 0 ≤ α ≤ C, Σ yα = 0.  Its gradient is
+    ``G* = Qα − 1 = −1 + y ∘ K (y ∘ α)``, so αᵀQα = α·(G* + 1) and the objective is ½ α·(G* − 1).
+    K is evaluated with direct-difference distances and the exponent scale read back from the
+    stored f32 (see the section comment).  Returns a dict: ``G`` (per point), ``obj``, ``sya``
+    (Σ yα), ``gap``, ``gmax_up``, ``gmax_low``, ``rho`` (:func:`svc_kkt` of α and G*).
+
+    Up to ``WS_LONGDOUBLE_MAX`` points everything is longdouble.  Above, K (y∘α) runs in f64 row
+    chunks over the columns with α ≠ 0: a row's f64 sum is off by at most nSV·2⁻⁵³·Σ_c α_c K_tc, while
+    every budget it is compared with (:func:`ws_gupdate_budget`) holds a term U·Σ_c |Δα_c| K_tc with
+    U = 2⁻²⁴ per update and the coefficients moved at least once in total: the ratio is
+    nSV·2⁻²⁹ ≈ 2e-9·nSV, below 1e-4 of the budget for any nSV this oracle can afford."""
+    np = _np()
+    L = np.longdouble
+    alpha = np.asarray(alpha, dtype=np.float64)
+    l = alpha.shape[0]
+    pos, y, C = _ws_labels(l, npos, Cp, Cn)
+    T = L if l <= WS_LONGDOUBLE_MAX else np.float64
+    e2 = np.float32(ngl2e_f32)
+    G = (-1 + y.astype(T) * ws_kernel_matvec(Z32, e2, y * alpha, T)).astype(L)
+    a = alpha.astype(L)
+    out = svc_kkt(a, G, npos, Cp, Cn)
+    out.update(G=G, obj=(a * (G - 1)).sum() / 2, sya=(y.astype(L) * a).sum())
+    return out
+
+
+def ws_kernel_error(Z32, ngl2e_f32, cols=None, rows=None):
+    """``(K, dK)`` [rows (default all), cols], f64: the kernel values and the forward bound of svm_ws.hip's f32
+    evaluation ``exp2(min(fma(k2, a·b, sn_a + sn_b), 0))`` with k2 = −2·ngl2e (exact, a power of two
+    times an f32), a·b an F-term f32 fma chain from 0 and sn_x = fl(ngl2e·fl_chain(‖x‖²)) — the
+    expression whose bound :func:`_rbf_core` derives for inference, without its term for rounding
+    γ·log2 e (here the stored f32 IS the scale).  In base-2 exponent units, with g2 = −ngl2e and
+    n-term chains costing γ_n = nU/(1 − nU):
+
+    * the two ‖x‖² chains and their products with ngl2e: g2·γ_{F+1}·(‖a‖² + ‖b‖²);
+    * the rounding of sn_a + sn_b: g2·U·(‖a‖² + ‖b‖²);
+    * the dot chain through k2: 2·g2·γ_F·|a|·|b|;
+    * the final fma: U·g2·(‖a‖² + ‖b‖² + 2|a|·|b|) at most;
+
+    together ≤ g2·γ_{F+3}·mag, mag = ‖a‖² + ‖b‖² + 2|a|·|b| (the ``(F+3)·U·mag`` term of
+    ``_rbf_core``).  The clamp at 0 only moves the exponent towards the true one (≤ 0).  Then
+    exp2's own error: K̂ = K·2^δ·(1 + ε), |ε| ≤ EPS_EXP2, plus _TINY for a flushed result.  This
+    function's own f64 Gram-form distances are off by ≤ (F+2)·2⁻⁵²·mag, added to δ."""
+    np = _np()
+    Z = np.asarray(Z32, dtype=np.float32).astype(np.float64)
+    F = Z.shape[1]
+    B = Z if cols is None else Z[cols]
+    if rows is not None:
+        Z = Z[rows]
+    g2 = -float(np.float32(ngl2e_f32))
+    na, nb = (Z * Z).sum(1), (B * B).sum(1)
+    cross = np.abs(Z) @ np.abs(B).T
+    mag = na[:, None] + nb[None, :] + 2 * cross
+    d2 = np.maximum(na[:, None] + nb[None, :] - 2 * (Z @ B.T), 0.0)
+    n = F + 3
+    de = g2 * mag * (n * _U / (1 - n * _U) + (F + 2) * 2.0 ** -52)
+    with np.errstate(under="ignore"):
+        K = np.exp2(-g2 * d2)
+    x = np.expm1(math.log(2.0) * de)
+    return K, K * (x + EPS_EXP2 + x * EPS_EXP2) + _TINY
+
+
+def ws_gupdate_budget(Z32, ngl2e_f32, dalpha, ncp, order=None, npos=None, rows=None):
+    """Per-row forward error bound of ONE gradient update of svm_ws.hip,
+    ``G_t += y_t·Σ_c fl32(y_c Δα_c)·K̂_tc`` accumulated by f32 fmas over the ``ncp`` staged columns
+    (changed coefficients padded to a multiple of 32), then added to the f64 G:
+
+    * the kernel values: Σ_c |Δα_c|·dK_tc (:func:`ws_kernel_error`);
+    * the coefficient rounded to f32 (``wdc`` is float): U·Σ_c |Δα_c|·K̂_tc;
+    * the f32 accumulation.  Without ``order``, the worst case of any summation of ncp terms:
+      γ_ncp·Σ_c |Δα_c|·K̂_tc, γ_n = nU/(1 − nU) (at 1,024 columns this term is 6e-5 of the sum
+      of magnitudes and dominates everything else by an order of magnitude).  With ``order`` — the
+      changed points in the order the solver staged them (working-set slot order) — and ``npos``,
+      the kernel's real summation tree: staged position p goes to half h = (p/4) mod 2 of a lane
+      pair; each half is ONE sequential chain pa = fma(cf_p, K̂_p, pa), whose k-th step rounds
+      once, by ≤ U·|ŝ_k| with ŝ_k the computed partial sum, and the halves are added once.  With
+      s_k the exact signed partial sum of y_c Δα_c K_tc, |ŝ_k| ≤ |s_k| + Σ_{i≤k}|Δα_i|(dK_i +
+      U·K̂_i) + γ_n·Σ_{i≤k}|Δα_i|K̂_i (n = the chain's length), so the chain costs
+      U·Σ_k [that bound] and the final add U·(1 + γ_n)·Σ_c|Δα_c|K̂_tc at most.  Padding columns
+      carry cf = 0: fma(0, ·, pa) = pa exactly.  Signed partial sums of a gradient update cancel
+      like a random walk, which the worst case cannot see;
+
+    with K̂ ≤ K + dK.  The f64 add to G (2⁻⁵³·|G_t|) is left to the caller, who knows G.  Budgets
+    add over rounds.  ``rows``: bound these rows only.  A seeded start (``ws_seed``) is the
+    worst-case expression with Δα = the seed and ncp = 256: at most 256 compacted coefficients per
+    f32 partial, the partials summed in f64.
+
+    Measured on an MI355X (tests/test_svm_ws_reference_gpu.py, summation-tree form, every round of
+    every case): the largest |G_dev − G*| / cumulative budget is 0.12 (0.029 at the end-to-end
+    tests' sizes, 0.013 after a seed)."""
+    np = _np()
+    sd = np.asarray(dalpha, dtype=np.float64)
+    d = np.abs(sd)
+    l = d.shape[0] if rows is None else len(rows)
+    cols = np.flatnonzero(d != 0) if order is None else np.asarray(order, dtype=np.int64)
+    if cols.size == 0:
+        return np.zeros(l)
+    K, dK = ws_kernel_error(Z32, ngl2e_f32, cols, rows)
+    w = d[cols]
+    Kh = K + dK
+    term = dK @ w + _U * (Kh @ w)
+    if order is None:
+        n = float(ncp)
+        return term + n * _U / (1 - n * _U) * (Kh @ w)
+    assert npos is not None and np.array_equal(np.sort(cols), np.flatnonzero(d != 0))
+    sgn = np.where(cols < int(npos), 1.0, -1.0) * sd[cols]
+    half = (np.arange(cols.size) // 4) % 2
+    acc = np.zeros(l)
+    for h in (0, 1):
+        ix = np.flatnonzero(half == h)
+        if ix.size == 0:
+            continue
+        n = float(ix.size)
+        gam = n * _U / (1 - n * _U)
+        S = np.abs(np.cumsum(K[:, ix] * sgn[ix][None, :], axis=1))
+        E = np.cumsum((dK[:, ix] + _U * Kh[:, ix]) * w[ix][None, :], axis=1)
+        P = np.cumsum(Kh[:, ix] * w[ix][None, :], axis=1)
+        acc += _U * (S + E + gam * P).sum(1)
+    n = float((cols.size + 1) // 2)
+    return term + acc + _U * (1 + n * _U / (1 - n * _U)) * (Kh @ w)
+
+
+def ws_okey(v):
+    """The solver's order-preserving u32 key of the f32 rounding of ``v`` (common.h f32_okey)."""
+    np = _np()
+    u = np.asarray(v, dtype=np.float64).astype(np.float32).view(np.uint32)
+    return u ^ np.where(u >> 31 != 0, np.uint32(0xFFFFFFFF), np.uint32(0x80000000))
+
+
+WS_KEY_BITS = 22   # two 11-bit radix levels: the selector ranks keys by their top 22 bits
+
+
+def ws_select_oracle(alpha, G, npos, Cp, Cn, Q, prev, key_bits=WS_KEY_BITS):
+    """The working-set selection rule of svm_ws.hip, from the α and G the selector saw.
+
+    1. keys: the f32 values of −yG for the members of I_up and of yG for the members of I_low
+       (membership from the f64 α, :func:`svc_kkt`), as order-preserving u32 (:func:`ws_okey`);
+    2. the min(Q/4, n_up) largest up keys;
+    3. the min(Q/4, n_low) largest low keys, WITHOUT the positions already taken for up: the
+       threshold is found over every member of I_low, the up picks are then left out and not
+       replaced, so the low list may be shorter than Q/4;
+    4. keys are ranked by their top ``key_bits`` bits (the selector's two 11-bit radix levels resolve
+       no more: within a 2⁻¹³ relative window below the threshold, keys are ties).  With T the
+       truncated key of the k-th largest member and ``above`` the members over T, every free
+       position over T is taken and then the first k − above free ties at T in position order;
+    5. then the previous round's new picks ``prev`` that were not picked again, in their old order.
+
+    Returns ``(up, low, carried)``: the new up and low picks in position order and the carried-over
+    sequence (int64).  With an empty I_up or I_low the selector stops: all three are empty."""
+    np = _np()
+    alpha = np.asarray(alpha, dtype=np.float64)
+    G = np.asarray(G, dtype=np.float64)
+    l = alpha.shape[0]
+    pos, y, C = _ws_labels(l, npos, Cp, Cn)
+    yG = np.where(pos, G, -G)
+    up = np.where(pos, alpha < C, alpha > 0)
+    low = np.where(pos, alpha > 0, alpha < C)
+    sh = np.uint32(32 - key_bits)
+    ku = np.where(up, ws_okey(-yG), np.uint32(0))
+    kl = np.where(low, ws_okey(yG), np.uint32(0))
+    e = np.zeros(0, dtype=np.int64)
+    n_up, n_low = int((ku != 0).sum()), int((kl != 0).sum())
+    if n_up == 0 or n_low == 0:
+        return e, e, e
+
+    taken = np.zeros(l, dtype=bool)
+
+    def top(k, count):
+        kt = (k >> sh).astype(np.int64)
+        member = k != 0
+        T = np.sort(kt[member])[::-1][count - 1]
+        need = count - int((member & (kt > T)).sum())
+        free = member & ~taken
+        return np.sort(np.concatenate([np.flatnonzero(free & (kt > T)), np.flatnonzero(free & (kt == T))[:need]]))
+
+    pu = top(ku, min(Q // 4, n_up))
+    taken[pu] = True
+    pl = top(kl, min(Q // 4, n_low))
+    taken[pl] = True
+    prev = np.asarray(prev, dtype=np.int64)
+    return pu, pl, prev[~taken[prev]] if prev.size else e
