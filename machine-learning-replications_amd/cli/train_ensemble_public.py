@@ -14,7 +14,9 @@ cohort is generated (``--rows``, ``--features``).  Extras: ``--device cuda``, ``
 and thresholded rates from N bootstrap resamples, and a bootstrap band on the ROC figure;
 ``--bootstrap-seed``, ``--stratified``), ``--calibration`` (Brier, O:E, calibration intercept and
 slope, ECE and net benefit of the held-out risks, a reliability and a decision-curve figure;
-intervals from the same resamples with ``--bootstrap N``); under ``torchrun`` the development rows are sharded
+intervals from the same resamples with ``--bootstrap N``), ``--compare`` (is the stack better than each of
+its base learners: paired ΔAUROC, ΔAP, NRI and IDI on the same resamples, DeLong's test and one ROC
+figure of all four models; points and DeLong only with ``--bootstrap 0``); under ``torchrun`` the development rows are sharded
 over ranks.
 """
 from __future__ import annotations
@@ -51,6 +53,10 @@ def main(argv=None, script_dir=None) -> int:
     ap.add_argument("--calibration", action="store_true",
                     help="report Brier, O:E, calibration intercept/slope, ECE and net benefit of the held-out "
                          "risks, with two figures; with --bootstrap N, their confidence intervals")
+    ap.add_argument("--compare", action="store_true",
+                    help="compare the stack with each base learner on the held-out rows: paired differences "
+                         "(AUROC, AP, NRI, IDI, ...) with DeLong's test and one ROC figure; with --bootstrap N, "
+                         "their confidence intervals and p-values from the same resamples")
     ap.add_argument("--calibration-bins", type=int, default=10)
     ap.add_argument("--calibration-thresholds", type=int, default=99)
     a = ap.parse_args(argv)
@@ -94,14 +100,19 @@ def main(argv=None, script_dir=None) -> int:
     # T:31: numpy's GLOBAL generator seeded with init_rs — liblinear's seeds ('lg', random_state=None)
     # are drawn from it, six times, in the stacking fit's order
     np.random.seed(cfg.seed)
-    res = develop(X_dev, y_dev, X_sel, y_sel, names, device=device, group=group, cfg=cfg)
-    if a.plots or a.bootstrap or a.calibration:
+    res = develop(X_dev, y_dev, X_sel, y_sel, names, device=device, group=group, cfg=cfg,
+                  **({"keep_bases": True} if a.compare else {}))
+    if a.plots or a.bootstrap or a.calibration or a.compare:
         # collectives on EVERY rank (before the rank-0 block); only rank 0 draws
         p_all = res.proba_sel
         y_all = torch.as_tensor(y_sel, device=p_all.device)
         if group is not None:
             p_all = pdist.all_gather_rows(p_all[:, None], group)[:, 0]
             y_all = pdist.all_gather_rows(y_all.to(p_all.dtype)[:, None], group)[:, 0]
+        if a.compare:
+            bases_all = res.bases_sel
+            if group is not None:
+                bases_all = pdist.all_gather_rows(bases_all, group)
     if rank == 0:
         print("Important Features")
         print(np.array(res.selected_names, dtype=object))
@@ -138,6 +149,25 @@ def main(argv=None, script_dir=None) -> int:
                 nb = {"point": dcv["net_benefit"][g], "lo": dcv["net_benefit_lo"][g], "hi": dcv["net_benefit_hi"][g]}
                 at.append(f"t = {dcv['thresholds'][g]:.2f}: {cell(nb)} vs treat-all {dcv['net_benefit_all'][g]:.4f}")
             print("net benefit   " + "   ".join(at))
+        comp = None
+        if a.compare:
+            models = {"stack": p_all.to(bases_all.dtype)}
+            models.update({name: bases_all[:, k] for k, name in enumerate(res.base_names)})
+            comp = metrics.compare_ci(y_all, models, "stack", n_boot=a.bootstrap, seed=a.bootstrap_seed,
+                                      stratified=a.stratified)
+            lvl = f"{100 * (1 - comp['alpha']):g}% CI"
+
+            def diff(v, delong=None):
+                if v is None:
+                    return "n/a"
+                notes = [f"{lvl} {v['lo']:+.4f}–{v['hi']:+.4f}", f"p = {v['p']:.4f}"] if a.bootstrap else []
+                if delong is not None:
+                    notes.append(f"DeLong p = {delong['p']:.4f}")
+                return f"{v['point']:+.4f}" + (f" ({', '.join(notes)})" if notes else "")
+            for name in res.base_names:
+                c = comp["comparisons"][name]
+                print(f"stack vs {name}: ΔAUROC {diff(c['delta_auroc'], c['delong'])}   ΔAP {diff(c['delta_ap'])}"
+                      f"   NRI {diff(c['nri'])}   IDI {diff(c['idi'])}")
         if a.timings:
             print(res.timer.table())
         if a.plots:
@@ -145,6 +175,8 @@ def main(argv=None, script_dir=None) -> int:
             print("plots:", metrics.save_plots(y_all, p_all, a.plots, band=band))
             if cal is not None:
                 print("calibration plots:", metrics.save_calibration_plots(cal, a.plots))
+            if comp is not None:
+                print("comparison plot:", metrics.save_compare_plot(y_all, models, a.plots))
         if a.save_model:
             from ..io.checkpoint import save_checkpoint
             model = res.model
@@ -159,6 +191,8 @@ def main(argv=None, script_dir=None) -> int:
                     line["bootstrap"] = ci
                 if cal is not None:
                     line["calibration"] = cal
+                if comp is not None:
+                    line["compare"] = comp
                 f.write(json.dumps(line) + "\n")
     pdist.shutdown()
     return 0

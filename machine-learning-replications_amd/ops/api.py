@@ -9,7 +9,7 @@ from .packing import pack_forest, pack_stack, pack_svs
 
 __all__ = ["rbf_decision", "svc_proba1", "tree_raw", "expit", "pack_svs", "pack_forest", "pack_stack",
            "stack_infer", "stack_shapley", "weighted_moments", "bootstrap_metrics",
-           "bootstrap_calibration"]
+           "bootstrap_calibration", "bootstrap_compare"]
 
 
 def _c(t: torch.Tensor, dtype) -> torch.Tensor:
@@ -340,6 +340,92 @@ def _calibration_device(y, score, *, seed, stratified, bins, thresholds, b0, b1,
                                 pl.bin_end.data_ptr(), pl.thr_prefix.data_ptr(), n, pl.p0, K, T,
                                 ref._seed_i64(seed), b0, B, int(use_lds), ws.data_ptr() if ws is not None else 0,
                                 slices, *(t.data_ptr() for t in out), int(grid), stream_ptr(dev))
+    return out
+
+
+COMPARE_LDS_ROWS = 13000           # rows whose three u32 arrays fit beside the kernel's 1,664 B of scratch (csrc/compare.hip)
+COMPARE_MAX_MODELS = 8
+_COMPARE_FORCE_GLOBAL = False      # tests: take the global-workspace path below the LDS limit too
+
+
+def bootstrap_compare(y, scores, n_boot: int, *, seed: int = 0, stratified: bool = False, threshold: float = 0.5,
+                      b0: int = 0, b1=None, grid: int = 0, stream=None):
+    """Bootstrap replicates ``b0:b1`` (default all ``n_boot``) of the held-out metrics of ``M`` score
+    columns ``scores [M, n]`` (f32 or f64) for binary labels ``y [n]``, all scored on the SAME
+    resamples: those of :func:`bootstrap_metrics` for the same ``seed``, mode and replicate.  Column 0
+    is the reference model, columns 1..M−1 its comparators.
+
+    Returns a :class:`reference.CompareBootstrap` (a tuple with named fields): ``auroc [B, M]`` =
+    ``a2 / (2·P_b·N_b)`` and ``ap [B, M]`` (f64; NaN for a degenerate replicate), the exact doubled
+    AUROC numerators ``a2 [B, M]``, the class totals ``pn [B, 2]``, ``conf [B, M, 4]`` = TP, FP, FN, TN at
+    ``score > threshold``, ``reclass [B, M, 4]`` = (eu, ed, nu, nd): drawn events above the threshold
+    under column 0 but not under column m (the reference moves the event up), the reverse, and the same
+    two patterns over the drawn non-events (column 0: zeros), and ``sums [B, M, 3]`` (f64) = Σc·p over
+    the drawn positives, over the drawn negatives, and Σc·(p − y)².
+    ``stream``, if given, is a raw HIP stream handle: everything is enqueued on it."""
+    if y.dim() != 1 or scores.dim() != 2 or y.numel() != scores.shape[1]:
+        raise ValueError(f"bootstrap_compare: y {tuple(y.shape)} must be [n] and scores {tuple(scores.shape)} "
+                         "[M, n] of one length n")
+    M, n = scores.shape
+    if not 1 <= M <= COMPARE_MAX_MODELS:
+        raise ValueError(f"bootstrap_compare: scores has M = {M} columns outside 1..{COMPARE_MAX_MODELS}")
+    if n == 0:
+        raise ValueError("bootstrap_compare: y and scores are empty (n = 0)")
+    if n > BOOTSTRAP_MAX_N:
+        raise ValueError(f"bootstrap_compare: y has {n} rows, the limit is n <= {BOOTSTRAP_MAX_N}")
+    if y.device != scores.device:
+        raise ValueError("bootstrap_compare: y and scores must be on the same device")
+    if not scores.is_floating_point() or not bool(torch.isfinite(scores).all()):
+        raise ValueError("bootstrap_compare: scores must be finite floating point")
+    if not bool(((y == 0) | (y == 1)).all()):
+        raise ValueError("bootstrap_compare: y must hold labels 0 and 1 only")
+    n_boot = int(n_boot)
+    if not 1 <= n_boot <= BOOTSTRAP_MAX_B:
+        raise ValueError(f"bootstrap_compare: n_boot = {n_boot} outside 1..{BOOTSTRAP_MAX_B}")
+    b1 = n_boot if b1 is None else int(b1)
+    b0 = int(b0)
+    if not 0 <= b0 <= b1 <= n_boot:
+        raise ValueError(f"bootstrap_compare: b0:b1 = {b0}:{b1} is not a range within 0..n_boot = {n_boot}")
+    if threshold != threshold:
+        raise ValueError("bootstrap_compare: threshold is NaN")
+    if stratified:
+        P = int((y == 1).sum())
+        if P == 0 or P == n:
+            raise ValueError("bootstrap_compare: stratified resampling needs both classes in y")
+    kw = dict(seed=seed, stratified=bool(stratified), threshold=float(threshold), b0=b0, b1=b1)
+    if not scores.is_cuda:
+        return ref.bootstrap_compare(y, scores, n_boot, **kw)
+    if stream is not None:
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=scores.device)):
+            return _compare_device(y, scores, grid=grid, **kw)
+    return _compare_device(y, scores, grid=grid, **kw)
+
+
+def _compare_device(y, scores, *, seed, stratified, threshold, b0, b1, grid):
+    """Validated ``cuda`` inputs; everything is enqueued on torch's current stream."""
+    from . import ext, stream_ptr
+    dev = scores.device
+    pl = ref.ComparePlan(y, scores, stratified, threshold)
+    n, M, B = pl.n, pl.M, b1 - b0
+    f64, i64 = torch.float64, torch.int64
+
+    def e(*shape, dtype):
+        return torch.empty(*shape, dtype=dtype, device=dev)
+    out = ref.CompareBootstrap(e(B, M, dtype=f64), e(B, M, dtype=f64), e(B, M, dtype=i64), e(B, 2, dtype=i64),
+                               e(B, M, 4, dtype=i64), e(B, M, 4, dtype=i64), e(B, M, 3, dtype=f64))
+    if B == 0:
+        return out
+    use_lds = n <= COMPARE_LDS_ROWS and not _COMPARE_FORCE_GLOBAL
+    ws, slices = None, 0
+    if not use_lds:
+        ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+        slices = max(1, min(B, 2 * ncu, BOOTSTRAP_WS_BYTES // (12 * n)))
+        ws = torch.empty(slices, 3 * n, dtype=torch.int32, device=dev)
+    ext().bootstrap_compare(pl.y.data_ptr(), pl.rowmap.data_ptr() if pl.rowmap is not None else 0,
+                            pl.order.data_ptr(), pl.ys.data_ptr(), pl.gfirst.data_ptr(), pl.glast.data_ptr(),
+                            pl.k0.data_ptr(), pl.hi.data_ptr(), pl.p.data_ptr(), n, pl.p0, M, ref._seed_i64(seed),
+                            b0, B, int(use_lds), ws.data_ptr() if ws is not None else 0, slices,
+                            *(t.data_ptr() for t in out), int(grid), stream_ptr(dev))
     return out
 
 

@@ -215,4 +215,10 @@ HFENS_OP(bootstrap_calibration, (uintptr_t y, uintptr_t map, uintptr_t p, uintpt
                                  int use_lds, uintptr_t ws, long long ws_slices, uintptr_t pn, uintptr_t brier,
                                  uintptr_t sum_p, uintptr_t bin_n, uintptr_t bin_pos, uintptr_t bin_sum_p, uintptr_t dc,
                                  uintptr_t status, uintptr_t coef, uintptr_t iters, int grid, uintptr_t stream))
+HFENS_OP(compare_lds_rows, (uintptr_t out))
+HFENS_OP(bootstrap_compare, (uintptr_t y, uintptr_t rowmap, uintptr_t order, uintptr_t ys, uintptr_t gfirst,
+                             uintptr_t glast, uintptr_t k0, uintptr_t hi, uintptr_t p, long long n, long long p0, int M,
+                             long long seed, long long b0, long long nb, int use_lds, uintptr_t ws,
+                             long long ws_slices, uintptr_t auroc, uintptr_t ap, uintptr_t a2, uintptr_t pn,
+                             uintptr_t conf, uintptr_t reclass, uintptr_t sums, int grid, uintptr_t stream))
 #undef HFENS_OP

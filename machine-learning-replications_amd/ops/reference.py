@@ -1066,6 +1066,254 @@ def calibration_oracle(y, score, n_boot: int, *, seed: int = 0, stratified: bool
             "iters": np.array(out["iters"], dtype=np.int64)}
 
 
+# ---- paired bootstrap comparison of score columns -----------------------------------------------------
+# Same resampling law again (csrc/compare.hip draws what csrc/bootstrap.hip draws), the rows drawn ONCE
+# per replicate and every column scored on them.  Column 0 is the reference model.  Definitions shared
+# by the kernel, this mirror and the oracle, with hi_m = score_m > threshold:
+#   reclass[m] = (eu, ed, nu, nd): drawn events with hi_0 = 1, hi_m = 0 (the reference moves the event
+#                up) / with hi_0 = 0, hi_m = 1, and the same two patterns over the drawn non-events;
+#   sums[m]    = Σc·p over the drawn positives, Σc·p over the drawn negatives, Σc·(p − y)², folded in
+#                original row order: thread t of 1024 over rows [t·chunk, (t+1)·chunk), chunk =
+#                ceil(n/1024), then the 64 lanes of a wave by an xor tree, then the 16 waves in order.
+
+COMPARE_THREADS = 1024
+COMPARE_WAVE = 64
+
+
+class CompareBootstrap(tuple):
+    """The outputs of ``bootstrap_compare`` in order, also by name."""
+    _fields = ("auroc", "ap", "a2", "pn", "conf", "reclass", "sums")
+
+    def __new__(cls, *vals):
+        assert len(vals) == len(cls._fields)
+        return super().__new__(cls, vals)
+
+    def __getattr__(self, name):
+        try:
+            return self[self._fields.index(name)]
+        except ValueError:
+            raise AttributeError(name) from None
+
+
+class ComparePlan:
+    """What is prepared once per call for labels ``y [n]`` and score columns ``scores [M, n]``: by
+    original row ``y`` (uint8), ``p`` (f64 [M, n]) and ``hi`` (uint8 [M, n]: score > threshold); per
+    column its descending stable score order ``order`` (int32 [M, n]: position → row) and, in that
+    order, the labels ``ys`` (uint8) and every position's tie group ``gfirst``/``glast`` (int32);
+    ``k0`` (int32 [M]: rows scoring > threshold); ``rowmap`` (int32 [n]: the positives' rows, then the
+    negatives'; None in plain mode) and ``p0`` (draws j < p0 take the first stratum; plain: n)."""
+
+    def __init__(self, y: torch.Tensor, scores: torch.Tensor, stratified: bool, threshold: float):
+        dev = scores.device
+        M, n = scores.shape
+        s = scores.to(torch.float64).contiguous()
+        pos = y.to(dev) > 0
+        rows = torch.arange(n, device=dev)
+        order, ys, gf, gl = [], [], [], []
+        for m in range(M):
+            o = torch.argsort(s[m], descending=True, stable=True)
+            ss = s[m][o]
+            start = torch.ones(n, dtype=torch.bool, device=dev)
+            start[1:] = ss[1:] != ss[:-1]
+            firsts = torch.nonzero(start).squeeze(1)
+            gid = torch.cumsum(start.to(torch.int64), 0) - 1
+            lasts = torch.cat([firsts[1:] - 1, torch.tensor([n - 1], device=dev)])
+            order.append(o)
+            ys.append(pos[o])
+            gf.append(firsts[gid])
+            gl.append(lasts[gid])
+        self.n, self.M = n, M
+        self.y = pos.to(torch.uint8).contiguous()
+        self.p = s
+        self.hi = (s > threshold).to(torch.uint8).contiguous()
+        self.order = torch.stack(order).to(torch.int32).contiguous()
+        self.ys = torch.stack(ys).to(torch.uint8).contiguous()
+        self.gfirst = torch.stack(gf).to(torch.int32).contiguous()
+        self.glast = torch.stack(gl).to(torch.int32).contiguous()
+        self.k0 = (s > threshold).sum(1).to(torch.int32).contiguous()
+        self.P = int(pos.sum())
+        if stratified:
+            self.rowmap = torch.cat([rows[pos], rows[~pos]]).to(torch.int32).contiguous()
+            self.p0 = self.P
+        else:
+            self.rowmap = None
+            self.p0 = n
+
+
+def _compare_fold(t: torch.Tensor) -> torch.Tensor:
+    """Σ over the last axis of ``t [B, n]`` (f64) in the kernel's order: chunk, wave xor tree, waves."""
+    B, n = t.shape
+    T, W = COMPARE_THREADS, COMPARE_WAVE
+    chunk = (n + T - 1) // T
+    pad = torch.zeros(B, T * chunk, dtype=t.dtype, device=t.device)
+    pad[:, :n] = t
+    pad = pad.reshape(B, T, chunk)
+    acc = torch.zeros(B, T, dtype=t.dtype, device=t.device)
+    for k in range(chunk):
+        acc = acc + pad[:, :, k]
+    acc = acc.reshape(B, T // W, W)
+    lanes = torch.arange(W, device=t.device)
+    o = W // 2
+    while o > 0:
+        acc = acc + acc[:, :, lanes ^ o]
+        o //= 2
+    out = torch.zeros(B, dtype=t.dtype, device=t.device)
+    for w in range(T // W):
+        out = out + acc[:, w, 0]
+    return out
+
+
+def bootstrap_compare(y: torch.Tensor, scores: torch.Tensor, n_boot: int, *, seed: int = 0,
+                      stratified: bool = False, threshold: float = 0.5, b0: int = 0, b1=None,
+                      chunk_elems: int = 1 << 22):
+    """Vectorised torch mirror of the comparison kernel (and the host path of
+    ``ops.bootstrap_compare``, which validates): the counts by ``bincount`` over the draws of the law
+    above, indexed by original row, then per column the formulas of :func:`bootstrap_metrics` on the
+    counts gathered through that column's order, and the paired statistics of the header.  Returns a
+    :class:`CompareBootstrap` for replicates ``b0:b1``: ``auroc``, ``ap`` (f64) and ``a2`` (int64)
+    ``[B, M]``, ``pn [B, 2]``, ``conf [B, M, 4]`` (TP FP FN TN), ``reclass [B, M, 4]`` (eu ed nu nd; column
+    0 zero) and ``sums [B, M, 3]`` (f64).  Replicates are processed ``chunk_elems // n`` at a time."""
+    pl = ComparePlan(y, scores, stratified, threshold)
+    dev = scores.device
+    n, M = pl.n, pl.M
+    b1 = n_boot if b1 is None else b1
+    i64, f64 = torch.int64, torch.float64
+    rows = torch.arange(n, device=dev)
+    j = torch.arange(n, dtype=i64, device=dev)
+    head = j < pl.p0
+    mm = torch.where(head, pl.p0, n - pl.p0)
+    off = torch.where(head, 0, pl.p0)
+    rowmap = pl.rowmap.to(i64) if pl.rowmap is not None else rows
+    sd = torch.tensor(_seed_i64(seed), dtype=i64, device=dev)
+    yb = pl.y > 0
+    yf = pl.y.to(f64)
+    hi = pl.hi > 0
+    k0 = pl.k0.tolist()
+    nan = float("nan")
+    outs = [[] for _ in range(7)]
+    per = max(1, chunk_elems // n)
+    for c0 in range(b0, b1, per):
+        bs = torch.arange(c0, min(b1, c0 + per), dtype=i64, device=dev)
+        Bc = bs.numel()
+        u = _splitmix64_t(sd ^ _splitmix64_t((bs[:, None] << 40) ^ j[None, :]))
+        r = (((u >> 32) & 0xFFFFFFFF) * mm[None, :]) >> 32
+        at = rowmap[off[None, :] + r] + torch.arange(Bc, device=dev)[:, None] * n
+        cnt = torch.bincount(at.reshape(-1), minlength=Bc * n).reshape(Bc, n)
+        C = cnt.to(f64)
+        cols = [[] for _ in range(6)]
+        pn = None
+        for m in range(M):
+            o = pl.order[m].to(i64)
+            ys = pl.ys[m].to(i64)
+            ends = torch.nonzero(pl.glast[m].to(i64) == rows).squeeze(1)
+            f = pl.gfirst[m].to(i64)[ends]
+            prev = (f - 1).clamp(min=0)
+            cm = cnt[:, o]
+            cp = torch.cumsum(cm * ys, 1)
+            cn = torch.cumsum(cm * (1 - ys), 1)
+            Pb, Nb = cp[:, -1], cn[:, -1]
+            deg = (Pb == 0) | (Nb == 0)
+            TP, FP = cp[:, ends], cn[:, ends]
+            TP0 = torch.where(f > 0, cp[:, prev], 0)
+            FP0 = torch.where(f > 0, cn[:, prev], 0)
+            a2 = ((FP - FP0) * (TP + TP0)).sum(1)
+            auroc = a2.to(f64) / (2 * Pb * Nb).to(f64)
+            tot = TP + FP
+            term = torch.where(tot > 0, ((TP - TP0) * TP).to(f64) / tot.clamp(min=1).to(f64), 0.0)
+            ap = term.sum(1) / Pb.to(f64)
+            if k0[m] > 0:
+                tpc, fpc = cp[:, k0[m] - 1], cn[:, k0[m] - 1]
+            else:
+                tpc, fpc = torch.zeros_like(Pb), torch.zeros_like(Pb)
+            if m == 0:
+                pn = torch.stack([Pb, Nb], 1)
+            up, down = hi[0] & ~hi[m], ~hi[0] & hi[m]
+            rc = torch.stack([(cnt * (m_ & c_).to(i64)).sum(1) for m_, c_ in
+                              ((up, yb), (down, yb), (up, ~yb), (down, ~yb))], 1)
+            cpm = C * pl.p[m][None, :]
+            d = pl.p[m] - yf
+            sm = torch.stack([_compare_fold(torch.where(yb[None, :], cpm, 0.0)),
+                              _compare_fold(torch.where(yb[None, :], 0.0, cpm)),
+                              _compare_fold(C * (d * d)[None, :])], 1)
+            for o_, v in zip(cols, (torch.where(deg, nan, auroc), torch.where(deg, nan, ap), a2,
+                                    torch.stack([tpc, fpc, Pb - tpc, Nb - fpc], 1), rc, sm)):
+                o_.append(v)
+        au, ap_, a2_, cf, rc_, sm_ = (torch.stack(c, 1) for c in cols)
+        for o_, v in zip(outs, (au, ap_, a2_, pn, cf, rc_, sm_)):
+            o_.append(v)
+    if not outs[0]:
+        def e(*shape, dtype):
+            return torch.empty(*shape, dtype=dtype, device=dev)
+        return CompareBootstrap(e(0, M, dtype=f64), e(0, M, dtype=f64), e(0, M, dtype=i64), e(0, 2, dtype=i64),
+                                e(0, M, 4, dtype=i64), e(0, M, 4, dtype=i64), e(0, M, 3, dtype=f64))
+    return CompareBootstrap(*(torch.cat(o) for o in outs))
+
+
+def compare_oracle(y, scores, n_boot: int, *, seed: int = 0, stratified: bool = False, threshold: float = 0.5,
+                   b0: int = 0, b1=None):
+    """Independent oracle for the tests: ``a2``, ``ap`` and ``conf`` of every column come from
+    :func:`bootstrap_oracle` on that column alone (which materialises the resample itself);
+    ``reclass`` is counted row by row on the rows ``bootstrap_resample`` draws by comparing each drawn
+    score with the threshold; ``sums`` add the drawn rows' terms in ``numpy.longdouble``.  Returns numpy
+    arrays named as the op's outputs (``auroc``, ``ap``, ``sums`` longdouble, the rest int64) in a dict,
+    plus ``n_degenerate``."""
+    np = _np()
+    ld = np.longdouble
+    y = [int(v) for v in np.asarray(y).reshape(-1)]
+    S = np.asarray(scores, dtype=np.float64)
+    M = S.shape[0]
+    b1 = n_boot if b1 is None else b1
+    B = b1 - b0
+    per = [bootstrap_oracle(y, S[m], n_boot, seed=seed, stratified=stratified, threshold=threshold,
+                            grid_points=2, b0=b0, b1=b1) for m in range(M)]
+    reclass = np.zeros((B, M, 4), dtype=np.int64)
+    sums = np.zeros((B, M, 3), dtype=ld)
+    for b in range(b0, b1):
+        idx = bootstrap_resample(y, b, seed, stratified)
+        for m in range(M):
+            for i in idx:
+                p, p_ref, event = float(S[m][i]), float(S[0][i]), y[i] == 1
+                if m > 0 and p_ref > threshold and not p > threshold:
+                    reclass[b - b0, m, 0 if event else 2] += 1
+                if m > 0 and not p_ref > threshold and p > threshold:
+                    reclass[b - b0, m, 1 if event else 3] += 1
+                sums[b - b0, m, 0 if event else 1] += ld(p)
+                sums[b - b0, m, 2] += (ld(p) - ld(1 if event else 0)) ** 2
+    res = {"auroc": np.stack([o["auroc"] for o in per], 1).reshape(B, M),
+           "ap": np.stack([o["ap"] for o in per], 1).reshape(B, M),
+           "a2": np.stack([o["a2"] for o in per], 1).reshape(B, M), "pn": per[0]["pn"],
+           "conf": np.stack([o["conf"] for o in per], 1).reshape(B, M, 4), "reclass": reclass, "sums": sums}
+    res["n_degenerate"] = per[0]["n_degenerate"]
+    return res
+
+
+def delong_oracle(y, pa, pb):
+    """DeLong, DeLong and Clarke-Pearson's test of two correlated AUROCs by its O(P·N) structural
+    components, in ``numpy.longdouble``: ψ(x, z) = 1, ½, 0 for x >, =, < z; V10_i = mean_j ψ(x_i, z_j)
+    over the negatives, V01_j = mean_i ψ(x_i, z_j) over the positives; the variance of the AUROC
+    difference is (S10_aa + S10_bb − 2·S10_ab)/P + (S01_aa + S01_bb − 2·S01_ab)/N with the sample
+    covariances S (denominators P − 1 and N − 1).  Returns ``auc_a``, ``auc_b``, ``delta`` and ``se``."""
+    np = _np()
+    ld = np.longdouble
+    y = np.asarray(y).reshape(-1)
+    pos = y == 1
+    P, N = int(pos.sum()), int((~pos).sum())
+    V10, V01, auc = [], [], []
+    for s in (pa, pb):
+        s = np.asarray(s, dtype=np.float64).reshape(-1)
+        x, z = s[pos].astype(ld), s[~pos].astype(ld)
+        psi = (x[:, None] > z[None, :]).astype(ld) + (x[:, None] == z[None, :]).astype(ld) / ld(2)
+        V10.append(psi.sum(1) / ld(N))
+        V01.append(psi.sum(0) / ld(P))
+        auc.append(psi.sum() / ld(P) / ld(N))
+
+    def cov(u, v, k):
+        return ((u - u.mean()) * (v - v.mean())).sum() / ld(k - 1)
+    var = (cov(V10[0], V10[0], P) + cov(V10[1], V10[1], P) - 2 * cov(V10[0], V10[1], P)) / ld(P) \
+        + (cov(V01[0], V01[0], N) + cov(V01[1], V01[1], N) - 2 * cov(V01[0], V01[1], N)) / ld(N)
+    return {"auc_a": auc[0], "auc_b": auc[1], "delta": auc[0] - auc[1], "se": np.sqrt(max(var, ld(0)))}
+
+
 # ----------------------------------------------------------------------------- working-set SVC oracle
 # numpy only, written from libsvm's published rules (Fan, Chen, Lin 2005: the C-SVC dual, I_up / I_low,
 # m(α) − M(α), calculate_rho) and from the documented behaviour of ops/csrc/svm_ws.hip.  Nothing here

@@ -91,10 +91,13 @@ class DevelopResult:
     scores: Dict[str, float]
     timer: StageTimer
     n_train: int = 0
+    bases_sel: Optional[torch.Tensor] = None      # keep_bases: [n_sel, 3] f64 base-learner P(class 1)
+    base_names: Optional[List[str]] = None
 
 
 def develop(X_dev, y_dev, X_sel, y_sel, names, device="cpu", cfg: Optional[EnsembleConfig] = None,
-            timer: Optional[StageTimer] = None, group=None, evaluate: bool = True) -> DevelopResult:
+            timer: Optional[StageTimer] = None, group=None, evaluate: bool = True,
+            keep_bases: bool = False) -> DevelopResult:
     cfg = cfg or EnsembleConfig()
     timer = timer or StageTimer(enabled=True, device=device if str(device).startswith("cuda") else None)
     dev = torch.device(device)
@@ -219,10 +222,14 @@ def develop(X_dev, y_dev, X_sel, y_sel, names, device="cpu", cfg: Optional[Ensem
         # (the held-out rows are already gathered for the report, so the AUROC comes from them;
         # metrics.roc_auc_sharded is the R8 path for callers that keep scores sharded)
         scores = metrics.evaluate(ysel_all, proba_all)
+    bases, base_names = None, None
+    if keep_bases and evaluate:
+        bases = clf.transform(X_sel_optm)
+        base_names = [name for name, _ in clf.estimators]
     hmark("develop_end")
     dmarks_flush()
     n_train = X_dev.shape[0]
     if fit_group is not None:
         from .parallel import dist as pdist
         n_train = pdist.all_reduce_int(n_train, group)
-    return DevelopResult(clf, mask, fn_new, proba, report, scores, timer, n_train)
+    return DevelopResult(clf, mask, fn_new, proba, report, scores, timer, n_train, bases, base_names)
