@@ -5,7 +5,9 @@ inputs (ordered as the model's columns, ``predict_hf.py:5-27``) default to the
 shipped example patient and the probability is printed between ``#`` rules.
 Additions: ``--set NAME=VALUE`` overrides, ``--csv`` batched scoring, ``--device``
 (``cuda`` runs the gfx950 kernels), ``--model`` path, ``--explain [--background CSV]``
-(exact Shapley contribution of every variable, printed after the unchanged probability block).
+(exact Shapley contribution of every variable, printed after the unchanged probability block),
+``--what-if [NAMES]`` / ``--what-if-csv PATH`` (the patient's risk as one variable moves over its
+grid, everything else as entered) and ``--interactions [N]`` (Friedman's H² of variable pairs).
 """
 from __future__ import annotations
 
@@ -78,6 +80,38 @@ def format_importance(names, mean_abs) -> str:
     return "\n".join(lines)
 
 
+def format_what_if(w, p: int = 0) -> str:
+    """One line per variable (current value, risk now, lowest and highest risk along the grid and
+    where), sorted by ``highest − lowest``, descending."""
+    now = 100 * float(w.prediction[p])
+    rows = []
+    for i, k in enumerate(w.features):
+        risk, grid = w.risk[i][p].cpu(), w.grids[i].cpu()
+        lo, hi = int(risk.argmin()), int(risk.argmax())
+        rows.append((float(risk[hi]) - float(risk[lo]), i,
+                     f"  {w.feature_names[i]:<24s} {float(w.x[p, k]):>8g}  now {now:.2f} %"
+                     f"  lowest {100 * float(risk[lo]):.2f} % at {float(grid[lo]):g}"
+                     f"  highest {100 * float(risk[hi]):.2f} % at {float(grid[hi]):g}"))
+    lines = ["What if one variable changes, everything else as entered (risk along the variable's grid):"]
+    return "\n".join(lines + [r[2] for r in sorted(rows, key=lambda r: (-r[0], r[1]))])
+
+
+def write_what_if_csv(path, w, p: int = 0) -> None:
+    with open(path, "w") as f:
+        f.write("variable,value,risk,cohort_mean_risk\n")
+        for i in sorted(range(len(w.features)), key=lambda i: w.features[i]):   # model order
+            grid, risk, coh = w.grids[i].cpu().tolist(), w.risk[i][p].cpu().tolist(), w.cohort[i].cpu().tolist()
+            for v, r, c in zip(grid, risk, coh):
+                f.write(f"{w.feature_names[i]},{v:.9g},{r:.9g},{c:.9g}\n")
+
+
+def format_interactions(it, top: int) -> str:
+    lines = [f"Friedman's H2 of variable pairs over {it.n_rows} patients (strongest first):"]
+    for j, k, h in it.top(top):
+        lines.append(f"  {it.feature_names[j]:<24s} {it.feature_names[k]:<24s} {h:.4f}")
+    return "\n".join(lines)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--model", default=None, help="checkpoint path (default: assets/hf_predict_model.pkl)")
@@ -89,7 +123,21 @@ def main(argv=None) -> int:
     ap.add_argument("--background", default=None, metavar="CSV",
                     help="background cohort for --explain (default: 128 synthetic HF patients; "
                          "on --device cpu each background row costs seconds per patient)")
+    ap.add_argument("--what-if", nargs="?", const="", default=None, metavar="NAME,NAME",
+                    help="risk of the patient as each named variable (default: all) moves over its grid")
+    ap.add_argument("--what-if-csv", default=None, metavar="PATH",
+                    help="write the what-if curves: variable,value,risk,cohort_mean_risk")
+    ap.add_argument("--interactions", nargs="?", const=10, default=None, type=int, metavar="N",
+                    help="the N (default 10) strongest pairs by Friedman's H2, over the --csv cohort "
+                         "when given, else over the background (first 512 rows)")
     a = ap.parse_args(argv)
+    wi_names = None
+    if a.what_if:
+        wi_names = [nm for nm in a.what_if.split(",") if nm]
+        for nm in wi_names:
+            if nm not in PATIENT_PARAMS:
+                print(f"unknown clinical variable {nm!r}; expected one of {list(PATIENT_PARAMS)}", file=sys.stderr)
+                return 2
     if a.csv:
         from ..io.checkpoint import load_checkpoint
         X = np.loadtxt(a.csv, delimiter=",", ndmin=2)
@@ -100,6 +148,8 @@ def main(argv=None) -> int:
         if a.explain:
             ex = _explainer(a)
             print(format_importance(ex.feature_names, ex.mean_abs(X).cpu().tolist()))
+        if a.interactions is not None:
+            print(format_interactions(_explainer(a).interaction_strength(X), a.interactions))
         return 0
     params = OrderedDict(PATIENT_PARAMS)
     for kv in a.set:
@@ -114,6 +164,14 @@ def main(argv=None) -> int:
         e = _explainer(a).shap_values([vals])
         print(format_explanation(e.feature_names, vals, e.phi[0].cpu().tolist(), e.base_value,
                                  float(e.prediction[0])))
+    if a.what_if is not None or a.what_if_csv:
+        w = _explainer(a).what_if([[float(v) for v in params.values()]], wi_names)
+        if a.what_if is not None:
+            print(format_what_if(w))
+        if a.what_if_csv:
+            write_what_if_csv(a.what_if_csv, w)
+    if a.interactions is not None:
+        print(format_interactions(_explainer(a).interaction_strength(), a.interactions))
     return 0
 
 

@@ -8,7 +8,7 @@ from . import reference as ref
 from .packing import pack_forest, pack_stack, pack_svs
 
 __all__ = ["rbf_decision", "svc_proba1", "tree_raw", "expit", "pack_svs", "pack_forest", "pack_stack",
-           "stack_infer", "stack_shapley", "weighted_moments", "bootstrap_metrics",
+           "stack_infer", "stack_shapley", "stack_partial", "weighted_moments", "bootstrap_metrics",
            "bootstrap_calibration", "bootstrap_compare"]
 
 
@@ -164,7 +164,75 @@ def _stack_shapley_device(x, background, pk, return_values: bool, grid: int):
     return out + (v_all,) if return_values else out
 
 
-BOOTSTRAP_MAX_B = 1 << 24          # the replicate index shares the draw counter: b < 2^24
+PARTIAL_ICE_BYTES = 1 << 30        # largest ice [n, C] f32 that stack_partial returns
+
+
+def stack_partial(x, pk, feat, value, *, return_ice: bool = False, grid: int = 0, stream=None):
+    """Partial dependence of the fused stack's P(class 1) over the cohort ``x``.
+
+    ``x``: [n, F] f32 or f64 on ``pk``'s device; ``feat``: [C, 2] integer, ``value``: [C, 2] float, on
+    the same device.  Cell c substitutes ``value[c, s]`` for column ``feat[c, s]`` of every cohort row,
+    for each slot s with ``feat[c, s] != -1`` (−1: no substitution; ``(-1, ·, -1, ·)`` is the plain
+    row).  ``x`` and ``value`` are rounded to f32 as ``stack_infer`` does.  Returns ``pd [C]`` f64 =
+    ``(Σ_r ice[r, c]) / n`` summed over r = 0, 1, …, n−1 in that order, and with ``return_ice`` also
+    ``ice [n, C]`` = P of every hybrid row (f32 on the GPU: the value that is widened and summed;
+    f64 on the host).  ``stream``, if given, is a raw HIP stream handle: the kernel and the torch
+    ops around it all run on it."""
+    if x.dim() != 2 or feat.dim() != 2 or value.dim() != 2 or feat.shape[1] != 2 or value.shape != feat.shape:
+        raise ValueError("stack_partial: x must be [n, F], feat and value [C, 2]")
+    n, F = x.shape
+    C = feat.shape[0]
+    if F != pk.F:
+        raise ValueError(f"stack_partial: x has {F} features, model has {pk.F}")
+    if n < 1:
+        raise ValueError("stack_partial: the cohort needs at least one row")
+    if C < 1:
+        raise ValueError("stack_partial: at least one cell is needed")
+    if feat.is_floating_point() or feat.dtype == torch.bool or not value.is_floating_point():
+        raise ValueError("stack_partial: feat must be integer and value floating point")
+    if not (x.device == feat.device == value.device == pk.mean.device):
+        raise ValueError("stack_partial: x, feat, value and the packed model must be on the same device")
+    if bool(((feat < -1) | (feat >= F)).any()):
+        raise ValueError(f"stack_partial: feature indices must lie in [-1, {F})")
+    if bool(((feat[:, 0] == feat[:, 1]) & (feat[:, 0] >= 0)).any()):
+        raise ValueError("stack_partial: a cell substitutes the same column twice")
+    if not bool(torch.isfinite(value.to(torch.float32))[feat >= 0].all()):
+        raise ValueError("stack_partial: a substituted value is not finite")
+    if return_ice and 4 * n * C > PARTIAL_ICE_BYTES:
+        raise ValueError(f"stack_partial: ice [{n}, {C}] f32 exceeds {PARTIAL_ICE_BYTES} bytes")
+    if not x.is_cuda:
+        return ref.stack_partial(x, pk, feat, value, return_ice=return_ice)
+    if stream is not None:
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=x.device)):
+            return _stack_partial_device(x, pk, feat, value, return_ice, grid)
+    return _stack_partial_device(x, pk, feat, value, return_ice, grid)
+
+
+def _stack_partial_device(x, pk, feat, value, return_ice: bool, grid: int):
+    """Validated ``cuda`` inputs; everything is enqueued on torch's current stream."""
+    from . import ext, stream_ptr
+    dev = x.device
+    n, F = x.shape
+    C = feat.shape[0]
+    x32 = _c(x, torch.float32)
+    k32 = _c(feat, torch.int32)
+    v32 = _c(value, torch.float32)
+    pd = torch.empty(C, dtype=torch.float64, device=dev)
+    ice = torch.empty(n, C, dtype=torch.float32, device=dev) if return_ice else None
+    f, s, st = pk.forest, pk.sv, pk.stumps
+    ext().stack_partial(x32.data_ptr(), n, k32.data_ptr(), v32.data_ptr(), C, F, s.mp, f.n_trees, f.max_nodes,
+                        -pk.gamma * 1.4426950408889634, pk.svc_b, pk.probA, pk.probB, pk.gb_init, pk.gb_lr,
+                        pk.lr_b, pk.meta_w[0], pk.meta_w[1], pk.meta_w[2], pk.meta_b, pk.mean.data_ptr(),
+                        pk.inv_scale.data_ptr(), s.svt.data_ptr(), s.sn.data_ptr(), s.coef.data_ptr(),
+                        f.nodes.data_ptr(), f.values.data_ptr(), pk.lr_w.data_ptr(),
+                        st.off.data_ptr() if st is not None else 0,
+                        st.pairs.data_ptr() if st is not None else 0,
+                        st.base if st is not None else 0.0,
+                        pd.data_ptr(), ice.data_ptr() if ice is not None else 0, int(grid), stream_ptr(dev))
+    return (pd, ice) if return_ice else pd
+
+
+BOOTSTRAP_MAX_B = 1 << 24         # the replicate index shares the draw counter: b < 2^24
 BOOTSTRAP_MAX_N = 1 << 25          # keeps the doubled AUROC numerator below 2^53
 BOOTSTRAP_LDS_ROWS = 20000         # rows whose two u32 arrays fit the CU's 160 KiB LDS (csrc/bootstrap.hip)
 BOOTSTRAP_WS_BYTES = 1 << 30       # byte budget of the global workspace above that (8n bytes per resident workgroup)

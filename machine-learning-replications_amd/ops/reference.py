@@ -211,6 +211,33 @@ def stack_shapley(x: torch.Tensor, background: torch.Tensor, pk, return_values: 
     return out + (v,) if return_values else out
 
 
+# ----------------------------------------------------------------------------- partial dependence
+def stack_partial(x: torch.Tensor, pk, feat: torch.Tensor, value: torch.Tensor, return_ice: bool = False,
+                  chunk: int = 16384):
+    """fp64 mirror of ``ops.stack_partial``.  Cell c = ``(feat[c, 0], value[c, 0], feat[c, 1],
+    value[c, 1])``; its hybrid row of cohort row r is ``x[r]`` with column ``feat[c, s]`` set to
+    ``value[c, s]`` for each slot s whose index is not −1.  ``ice[r, c]`` = :func:`stack_infer` of that
+    row, ``pd[c]`` = the mean of ``ice[:, c]`` summed in row order.  ``x`` and ``value`` are first
+    rounded to f32, as the kernel sees them; the hybrid rows are materialised ``chunk`` at a time."""
+    x = x.to(torch.float32).to(torch.float64)
+    value = value.to(torch.float32).to(torch.float64)
+    feat = feat.to(torch.int64)
+    n, C = x.shape[0], feat.shape[0]
+    ice = torch.empty(n, C, dtype=torch.float64)
+    per = max(1, chunk // n)
+    rows = torch.arange(per)
+    for c0 in range(0, C, per):
+        c1 = min(C, c0 + per)
+        h = x[None, :, :].repeat(c1 - c0, 1, 1)                         # [cells, n, F]
+        for s in range(2):
+            k, v = feat[c0:c1, s], value[c0:c1, s]
+            on = (k >= 0).nonzero().flatten()
+            h[rows[:c1 - c0][on], :, k[on]] = v[on][:, None]
+        ice[:, c0:c1] = stack_infer(h.reshape(-1, x.shape[1]), pk).reshape(c1 - c0, n).t()
+    pd = torch.cumsum(ice, 0)[-1] / n                                   # Σ over r = 0, 1, …, n−1 in that order
+    return (pd, ice) if return_ice else pd
+
+
 # ----------------------------------------------------------------------------- KNN imputation
 def knn_impute1(fit, X, undecided_rel: float = 2.0 ** -45):
     """Brute-force 1-NN imputation (sklearn ``KNNImputer(n_neighbors=1)`` semantics, numpy
