@@ -239,6 +239,57 @@ BOOTSTRAP_WS_BYTES = 1 << 30       # byte budget of the global workspace above t
 _BOOTSTRAP_FORCE_GLOBAL = False    # tests: take the global-workspace path below the LDS limit too
 
 
+def _bootstrap_args(op: str, y, score, name: str, n_boot, b0, b1, stratified):
+    """The checks the three bootstrap ops share, on labels ``y [n]`` and ``score [n]`` (``name`` "score")
+    or ``[M, n]`` ("scores"); returns the normalised ``n_boot, b0, b1``."""
+    if name == "scores":
+        if y.dim() != 1 or score.dim() != 2 or y.numel() != score.shape[1]:
+            raise ValueError(f"{op}: y {tuple(y.shape)} must be [n] and scores {tuple(score.shape)} "
+                             "[M, n] of one length n")
+    elif y.dim() != 1 or score.dim() != 1 or y.numel() != score.numel():
+        raise ValueError(f"{op}: y {tuple(y.shape)} and score {tuple(score.shape)} must be "
+                         "1-D of one length")
+    n = y.numel()
+    if n == 0:
+        raise ValueError(f"{op}: y and {name} are empty (n = 0)")
+    if n > BOOTSTRAP_MAX_N:
+        raise ValueError(f"{op}: y has {n} rows, the limit is n <= {BOOTSTRAP_MAX_N}")
+    if y.device != score.device:
+        raise ValueError(f"{op}: y and {name} must be on the same device")
+    if not score.is_floating_point() or not bool(torch.isfinite(score).all()):
+        raise ValueError(f"{op}: {name} must be finite floating point")
+    if not bool(((y == 0) | (y == 1)).all()):
+        raise ValueError(f"{op}: y must hold labels 0 and 1 only")
+    n_boot = int(n_boot)
+    if not 1 <= n_boot <= BOOTSTRAP_MAX_B:
+        raise ValueError(f"{op}: n_boot = {n_boot} outside 1..{BOOTSTRAP_MAX_B}")
+    b1 = n_boot if b1 is None else int(b1)
+    b0 = int(b0)
+    if not 0 <= b0 <= b1 <= n_boot:
+        raise ValueError(f"{op}: b0:b1 = {b0}:{b1} is not a range within 0..n_boot = {n_boot}")
+    if stratified:
+        P = int((y == 1).sum())
+        if P == 0 or P == n:
+            raise ValueError(f"{op}: stratified resampling needs both classes in y")
+    return n_boot, b0, b1
+
+
+def _bootstrap_workspace(dev, n: int, B: int, words: int):
+    """The global workspace of ``words`` u32 per row, one slice per workgroup that can be resident
+    within the byte budget; returns it and the number of slices."""
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    slices = max(1, min(B, 2 * ncu, BOOTSTRAP_WS_BYTES // (4 * words * n)))
+    return torch.empty(slices, words * n, dtype=torch.int32, device=dev), slices
+
+
+def _on_stream(stream, device, fn, *args, **kw):
+    """``fn(*args, **kw)`` with the raw HIP stream handle ``stream``, if given, as torch's current stream."""
+    if stream is None:
+        return fn(*args, **kw)
+    with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=device)):
+        return fn(*args, **kw)
+
+
 def bootstrap_metrics(y, score, n_boot: int, *, seed: int = 0, stratified: bool = False,
                       threshold: float = 0.5, grid_points: int = 101, b0: int = 0, b1=None,
                       grid: int = 0, stream=None):
@@ -246,7 +297,7 @@ def bootstrap_metrics(y, score, n_boot: int, *, seed: int = 0, stratified: bool 
     labels ``y [n]`` and scores ``score [n]`` (f32 or f64) on one device.
 
     Replicate b resamples n rows with replacement by the counter-based law of
-    ``csrc/bootstrap.hip`` (plain, or ``stratified``: P positives and N negatives drawn within
+    ``csrc/resample.h`` (plain, or ``stratified``: P positives and N negatives drawn within
     their class), so it does not depend on the range, grid or device it is computed in.  Returns
     ``auroc [B]`` = ``a2 / (2·P_b·N_b)`` and ``ap [B]`` (f64), the exact doubled AUROC numerator
     ``a2 [B]``, the class totals ``pn [B, 2]``, the confusion counts ``conf [B, 4]`` = TP, FP, FN,
@@ -254,43 +305,16 @@ def bootstrap_metrics(y, score, n_boot: int, *, seed: int = 0, stratified: bool 
     read at FPR = g/(grid_points − 1), the upper point of a vertical run.  A degenerate replicate
     (``P_b = 0`` or ``N_b = 0``; plain mode only) has NaN ``auroc``, ``ap`` and ``tpr``.
     ``stream``, if given, is a raw HIP stream handle: everything is enqueued on it."""
-    if y.dim() != 1 or score.dim() != 1 or y.numel() != score.numel():
-        raise ValueError(f"bootstrap_metrics: y {tuple(y.shape)} and score {tuple(score.shape)} must be "
-                         "1-D of one length")
-    n = score.numel()
-    if n == 0:
-        raise ValueError("bootstrap_metrics: y and score are empty (n = 0)")
-    if n > BOOTSTRAP_MAX_N:
-        raise ValueError(f"bootstrap_metrics: y has {n} rows, the limit is n <= {BOOTSTRAP_MAX_N}")
-    if y.device != score.device:
-        raise ValueError("bootstrap_metrics: y and score must be on the same device")
-    if not score.is_floating_point() or not bool(torch.isfinite(score).all()):
-        raise ValueError("bootstrap_metrics: score must be finite floating point")
-    if not bool(((y == 0) | (y == 1)).all()):
-        raise ValueError("bootstrap_metrics: y must hold labels 0 and 1 only")
-    n_boot = int(n_boot)
-    if not 1 <= n_boot <= BOOTSTRAP_MAX_B:
-        raise ValueError(f"bootstrap_metrics: n_boot = {n_boot} outside 1..{BOOTSTRAP_MAX_B}")
-    b1 = n_boot if b1 is None else int(b1)
-    b0 = int(b0)
-    if not 0 <= b0 <= b1 <= n_boot:
-        raise ValueError(f"bootstrap_metrics: b0:b1 = {b0}:{b1} is not a range within 0..n_boot = {n_boot}")
+    n_boot, b0, b1 = _bootstrap_args("bootstrap_metrics", y, score, "score", n_boot, b0, b1, stratified)
     G = int(grid_points)
     if not 2 <= G <= 65536:
         raise ValueError(f"bootstrap_metrics: grid_points = {G} outside 2..65536")
     if threshold != threshold:
         raise ValueError("bootstrap_metrics: threshold is NaN")
-    if stratified:
-        P = int((y == 1).sum())
-        if P == 0 or P == n:
-            raise ValueError("bootstrap_metrics: stratified resampling needs both classes in y")
     kw = dict(seed=seed, stratified=bool(stratified), threshold=float(threshold), grid_points=G, b0=b0, b1=b1)
     if not score.is_cuda:
         return ref.bootstrap_metrics(y, score, n_boot, **kw)
-    if stream is not None:
-        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=score.device)):
-            return _bootstrap_device(y, score, grid=grid, **kw)
-    return _bootstrap_device(y, score, grid=grid, **kw)
+    return _on_stream(stream, score.device, _bootstrap_device, y, score, grid=grid, **kw)
 
 
 def _bootstrap_device(y, score, *, seed, stratified, threshold, grid_points, b0, b1, grid):
@@ -309,11 +333,7 @@ def _bootstrap_device(y, score, *, seed, stratified, threshold, grid_points, b0,
     if B == 0:
         return auroc, ap, a2, pn, conf, tpr
     use_lds = n <= BOOTSTRAP_LDS_ROWS and not _BOOTSTRAP_FORCE_GLOBAL
-    ws, slices = None, 0
-    if not use_lds:
-        ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-        slices = max(1, min(B, 2 * ncu, BOOTSTRAP_WS_BYTES // (8 * n)))
-        ws = torch.empty(slices, 2 * n, dtype=torch.int32, device=dev)
+    ws, slices = (None, 0) if use_lds else _bootstrap_workspace(dev, n, B, 2)
     ext().bootstrap_metrics(pl.y.data_ptr(), pl.gfirst.data_ptr(), pl.glast.data_ptr(), pl.map.data_ptr(), n,
                             pl.p0, pl.k0, G, ref._seed_i64(seed), b0, B, int(use_lds),
                             ws.data_ptr() if ws is not None else 0, slices, auroc.data_ptr(), ap.data_ptr(),
@@ -342,45 +362,18 @@ def bootstrap_calibration(y, score, n_boot: int, *, seed: int = 0, stratified: b
     intercept and slope of the count-weighted logistic fit of y on logit(p) (p clamped to
     [1e-12, 1 − 1e-12]; NaN unless status 0) and its Newton step count ``iters [B]``.
     ``stream``, if given, is a raw HIP stream handle: everything is enqueued on it."""
-    if y.dim() != 1 or score.dim() != 1 or y.numel() != score.numel():
-        raise ValueError(f"bootstrap_calibration: y {tuple(y.shape)} and score {tuple(score.shape)} must be "
-                         "1-D of one length")
-    n = score.numel()
-    if n == 0:
-        raise ValueError("bootstrap_calibration: y and score are empty (n = 0)")
-    if n > BOOTSTRAP_MAX_N:
-        raise ValueError(f"bootstrap_calibration: y has {n} rows, the limit is n <= {BOOTSTRAP_MAX_N}")
-    if y.device != score.device:
-        raise ValueError("bootstrap_calibration: y and score must be on the same device")
-    if not score.is_floating_point() or not bool(torch.isfinite(score).all()):
-        raise ValueError("bootstrap_calibration: score must be finite floating point")
+    n_boot, b0, b1 = _bootstrap_args("bootstrap_calibration", y, score, "score", n_boot, b0, b1, stratified)
     if not bool(((score >= 0) & (score <= 1)).all()):
         raise ValueError("bootstrap_calibration: score must lie in [0, 1]")
-    if not bool(((y == 0) | (y == 1)).all()):
-        raise ValueError("bootstrap_calibration: y must hold labels 0 and 1 only")
-    n_boot = int(n_boot)
-    if not 1 <= n_boot <= BOOTSTRAP_MAX_B:
-        raise ValueError(f"bootstrap_calibration: n_boot = {n_boot} outside 1..{BOOTSTRAP_MAX_B}")
-    b1 = n_boot if b1 is None else int(b1)
-    b0 = int(b0)
-    if not 0 <= b0 <= b1 <= n_boot:
-        raise ValueError(f"bootstrap_calibration: b0:b1 = {b0}:{b1} is not a range within 0..n_boot = {n_boot}")
     K, T = int(bins), int(thresholds)
     if not 1 <= K <= CALIBRATION_MAX_BINS:
         raise ValueError(f"bootstrap_calibration: bins = {K} outside 1..{CALIBRATION_MAX_BINS}")
     if not 1 <= T <= CALIBRATION_MAX_THRESHOLDS:
         raise ValueError(f"bootstrap_calibration: thresholds = {T} outside 1..{CALIBRATION_MAX_THRESHOLDS}")
-    if stratified:
-        P = int((y == 1).sum())
-        if P == 0 or P == n:
-            raise ValueError("bootstrap_calibration: stratified resampling needs both classes in y")
     kw = dict(seed=seed, stratified=bool(stratified), bins=K, thresholds=T, b0=b0, b1=b1)
     if not score.is_cuda:
         return ref.bootstrap_calibration(y, score, n_boot, **kw)
-    if stream is not None:
-        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=score.device)):
-            return _calibration_device(y, score, grid=grid, **kw)
-    return _calibration_device(y, score, grid=grid, **kw)
+    return _on_stream(stream, score.device, _calibration_device, y, score, grid=grid, **kw)
 
 
 def _calibration_device(y, score, *, seed, stratified, bins, thresholds, b0, b1, grid):
@@ -399,11 +392,7 @@ def _calibration_device(y, score, *, seed, stratified, bins, thresholds, b0, b1,
     if B == 0:
         return out
     use_lds = n <= CALIBRATION_LDS_ROWS and not _CALIBRATION_FORCE_GLOBAL
-    ws, slices = None, 0
-    if not use_lds:
-        ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-        slices = max(1, min(B, 2 * ncu, BOOTSTRAP_WS_BYTES // (8 * n)))
-        ws = torch.empty(slices, 2 * n, dtype=torch.int32, device=dev)
+    ws, slices = (None, 0) if use_lds else _bootstrap_workspace(dev, n, B, 2)
     ext().bootstrap_calibration(pl.y.data_ptr(), pl.map.data_ptr(), pl.p.data_ptr(), pl.l.data_ptr(),
                                 pl.bin_end.data_ptr(), pl.thr_prefix.data_ptr(), n, pl.p0, K, T,
                                 ref._seed_i64(seed), b0, B, int(use_lds), ws.data_ptr() if ws is not None else 0,
@@ -431,42 +420,16 @@ def bootstrap_compare(y, scores, n_boot: int, *, seed: int = 0, stratified: bool
     two patterns over the drawn non-events (column 0: zeros), and ``sums [B, M, 3]`` (f64) = Σc·p over
     the drawn positives, over the drawn negatives, and Σc·(p − y)².
     ``stream``, if given, is a raw HIP stream handle: everything is enqueued on it."""
-    if y.dim() != 1 or scores.dim() != 2 or y.numel() != scores.shape[1]:
-        raise ValueError(f"bootstrap_compare: y {tuple(y.shape)} must be [n] and scores {tuple(scores.shape)} "
-                         "[M, n] of one length n")
-    M, n = scores.shape
+    n_boot, b0, b1 = _bootstrap_args("bootstrap_compare", y, scores, "scores", n_boot, b0, b1, stratified)
+    M = scores.shape[0]
     if not 1 <= M <= COMPARE_MAX_MODELS:
         raise ValueError(f"bootstrap_compare: scores has M = {M} columns outside 1..{COMPARE_MAX_MODELS}")
-    if n == 0:
-        raise ValueError("bootstrap_compare: y and scores are empty (n = 0)")
-    if n > BOOTSTRAP_MAX_N:
-        raise ValueError(f"bootstrap_compare: y has {n} rows, the limit is n <= {BOOTSTRAP_MAX_N}")
-    if y.device != scores.device:
-        raise ValueError("bootstrap_compare: y and scores must be on the same device")
-    if not scores.is_floating_point() or not bool(torch.isfinite(scores).all()):
-        raise ValueError("bootstrap_compare: scores must be finite floating point")
-    if not bool(((y == 0) | (y == 1)).all()):
-        raise ValueError("bootstrap_compare: y must hold labels 0 and 1 only")
-    n_boot = int(n_boot)
-    if not 1 <= n_boot <= BOOTSTRAP_MAX_B:
-        raise ValueError(f"bootstrap_compare: n_boot = {n_boot} outside 1..{BOOTSTRAP_MAX_B}")
-    b1 = n_boot if b1 is None else int(b1)
-    b0 = int(b0)
-    if not 0 <= b0 <= b1 <= n_boot:
-        raise ValueError(f"bootstrap_compare: b0:b1 = {b0}:{b1} is not a range within 0..n_boot = {n_boot}")
     if threshold != threshold:
         raise ValueError("bootstrap_compare: threshold is NaN")
-    if stratified:
-        P = int((y == 1).sum())
-        if P == 0 or P == n:
-            raise ValueError("bootstrap_compare: stratified resampling needs both classes in y")
     kw = dict(seed=seed, stratified=bool(stratified), threshold=float(threshold), b0=b0, b1=b1)
     if not scores.is_cuda:
         return ref.bootstrap_compare(y, scores, n_boot, **kw)
-    if stream is not None:
-        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=scores.device)):
-            return _compare_device(y, scores, grid=grid, **kw)
-    return _compare_device(y, scores, grid=grid, **kw)
+    return _on_stream(stream, scores.device, _compare_device, y, scores, grid=grid, **kw)
 
 
 def _compare_device(y, scores, *, seed, stratified, threshold, b0, b1, grid):
@@ -484,11 +447,7 @@ def _compare_device(y, scores, *, seed, stratified, threshold, b0, b1, grid):
     if B == 0:
         return out
     use_lds = n <= COMPARE_LDS_ROWS and not _COMPARE_FORCE_GLOBAL
-    ws, slices = None, 0
-    if not use_lds:
-        ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-        slices = max(1, min(B, 2 * ncu, BOOTSTRAP_WS_BYTES // (12 * n)))
-        ws = torch.empty(slices, 3 * n, dtype=torch.int32, device=dev)
+    ws, slices = (None, 0) if use_lds else _bootstrap_workspace(dev, n, B, 3)
     ext().bootstrap_compare(pl.y.data_ptr(), pl.rowmap.data_ptr() if pl.rowmap is not None else 0,
                             pl.order.data_ptr(), pl.ys.data_ptr(), pl.gfirst.data_ptr(), pl.glast.data_ptr(),
                             pl.k0.data_ptr(), pl.hi.data_ptr(), pl.p.data_ptr(), n, pl.p0, M, ref._seed_i64(seed),

@@ -1,10 +1,8 @@
 // Nonparametric bootstrap of the held-out calibration and decision-curve statistics: Brier score,
 // Σp (for O:E), the reliability bins, TP/FP at a grid of treat thresholds and the weighted
 // two-parameter logistic recalibration fit (Cox: logit P(y=1) = a + b·logit p), one workgroup per
-// replicate, on the resample bootstrap.hip draws for the same seed, mode and replicate.
-//
-//   draw j of replicate b over a stratum of m rows (the law of bootstrap.hip, bit for bit):
-//     u = splitmix64(seed ^ splitmix64((b << 40) ^ j)),  r = ((u >> 32)·m) >> 32   ∈ [0, m)
+// replicate, on the resample bootstrap.hip draws for the same seed, mode and replicate: both draw
+// through resample.h, where the law is stated.
 //
 // Per replicate: zero the counts → n integer atomicAdds → block-wide inclusive scan of the
 // (positive, negative) multiplicities, thread t owning rows [t·chunk, (t+1)·chunk); the same walk
@@ -22,32 +20,18 @@
 //   global  above that, workgroup w owns slice w of the caller's workspace (2n u32 per slice).
 // The Newton state lives in every thread: all of them fold the 16 wave partials in the same order
 // and take the same branches.  No float atomics; results are written with ordinary vector stores.
-#include "common.h"
-
-#include <algorithm>
+#include "resample.h"
 
 #pragma clang fp contract(off)   // the mirror rounds a + b·c twice; so does this file
 
 namespace hfens {
 
-constexpr int kCalThreads = 1024;
-constexpr int kCalWaves = kCalThreads / kWave;
 constexpr int kCalLdsRows = 20000;
-constexpr long long kCalMaxN = 1LL << 25;
-constexpr long long kCalMaxB = 1LL << 24;    // replicate index shares the counter with the draw
-constexpr int kCalLdsPerCu = 160 * 1024;
 constexpr int kCalStatic = 2176;             // sc_pn 128 + sc_ix 256 + sc_bs 256 + sc_nt 1536
 constexpr int kCalMaxIter = 50;
 constexpr int kCalMaxHalve = 40;
 constexpr double kCalStepTol = 1e-10;
 constexpr double kCalRise = 1e-12;
-
-__device__ __forceinline__ unsigned long long cal_splitmix64(unsigned long long x) {   // as bootstrap.hip
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
 struct CalArgs {
   const unsigned char* y;   // [n] labels in score order
@@ -117,7 +101,7 @@ __device__ __forceinline__ CalSums cal_pass(const CalArgs& A, const unsigned* cp
   __syncthreads();
   CalSums s{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll 2   // unrolled 16 times it holds 96 doubles in flight and spills
-  for (int w = 0; w < kCalWaves; ++w) {
+  for (int w = 0; w < kBootWaves; ++w) {
     s.dev += sc[w][0]; s.g0 += sc[w][1]; s.g1 += sc[w][2];
     s.h00 += sc[w][3]; s.h01 += sc[w][4]; s.h11 += sc[w][5];
   }
@@ -125,67 +109,35 @@ __device__ __forceinline__ CalSums cal_pass(const CalArgs& A, const unsigned* cp
 }
 
 template <bool kLds>
-__global__ __launch_bounds__(kCalThreads) void calibration_kernel(CalArgs A) {
+__global__ __launch_bounds__(kBootThreads) void calibration_kernel(CalArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned cal_lds[];
-  __shared__ unsigned sc_pn[kCalWaves][2];
-  __shared__ int sc_ix[kCalWaves][4];        // first/last drawn positive, first/last drawn negative
-  __shared__ double sc_bs[kCalWaves][2];     // Σc(p−y)², Σc·p
-  __shared__ double sc_nt[2][kCalWaves][6];
+  __shared__ unsigned sc_pn[kBootWaves][2];
+  __shared__ int sc_ix[kBootWaves][4];        // first/last drawn positive, first/last drawn negative
+  __shared__ double sc_bs[kBootWaves][2];     // Σc(p−y)², Σc·p
+  __shared__ double sc_nt[2][kBootWaves][6];
   const int n = A.n, K = A.K, T = A.T;
   unsigned* cp;   // counts, then cumulative positive multiplicity
   if constexpr (kLds) cp = cal_lds;
   else cp = A.ws + (size_t)blockIdx.x * 2 * (size_t)n;
   unsigned* cn = cp + n;   // cumulative negative multiplicity
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const int chunk = (n + kCalThreads - 1) / kCalThreads;
-  const int r0 = min(n, tid * chunk), r1 = min(n, r0 + chunk);
-  const double kNan = __longlong_as_double(0x7ff8000000000000ll);
+  const BootThread t = boot_thread(n);
+  const int tid = t.tid, lane = t.lane, wave = t.wave, r0 = t.r0, r1 = t.r1;
+  const double kNan = boot_nan();
 
   for (int bb = blockIdx.x; bb < A.nb; bb += gridDim.x) {
-    const unsigned long long b = (unsigned long long)(A.b0 + bb);
-    for (int i = tid; i < n; i += kCalThreads) cp[i] = 0u;
-    __syncthreads();
-    for (int j = tid; j < n; j += kCalThreads) {
-      const unsigned long long u = cal_splitmix64(A.seed ^ cal_splitmix64((b << 40) ^ (unsigned long long)j));
-      const bool head = j < A.p0;
-      const unsigned long long m = head ? A.p0 : n - A.p0;
-      const int r = (int)(((u >> 32) * m) >> 32);
-      atomicAdd(&cp[A.map[(head ? 0 : A.p0) + r]], 1u);
-    }
-    __syncthreads();
-
-    // block-wide inclusive scan of (positive, negative) multiplicities
-    unsigned sp = 0, sn = 0;
-    for (int i = r0; i < r1; ++i) {
-      const unsigned c = cp[i];
-      if (A.y[i]) sp += c; else sn += c;
-    }
-    unsigned ip = sp, in = sn;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const unsigned tp = __shfl_up(ip, o, kWave), tn = __shfl_up(in, o, kWave);
-      if (lane >= o) { ip += tp; in += tn; }
-    }
-    if (lane == kWave - 1) { sc_pn[wave][0] = ip; sc_pn[wave][1] = in; }
-    __syncthreads();
-    unsigned runp = ip - sp, runn = in - sn;
-    for (int w = 0; w < wave; ++w) { runp += sc_pn[w][0]; runn += sc_pn[w][1]; }
-    // the same walk: Brier and Σp partials, first and last drawn row of each class
+    boot_draw(cp, A.map, n, A.p0, A.seed, (unsigned long long)(A.b0 + bb));
+    // the scan's second walk also folds the Brier and Σp partials and finds the first and last drawn
+    // row of each class
     double sb = 0.0, sq = 0.0;
     int fpos = n, lpos = -1, fneg = n, lneg = -1;
-    for (int i = r0; i < r1; ++i) {
-      const unsigned c = cp[i];
-      const bool pos = A.y[i] != 0;
-      if (pos) runp += c; else runn += c;
-      cp[i] = runp;
-      cn[i] = runn;
-      if (c == 0u) continue;
+    boot_scan(cp, cn, A.y, t, sc_pn, [&](int i, unsigned c, bool pos) {
+      if (c == 0u) return;
       const double w = (double)c, pi = A.p[i];
       const double d = pi - (pos ? 1.0 : 0.0);
       sb += w * (d * d);
       sq += w * pi;
       if (pos) { fpos = min(fpos, i); lpos = i; } else { fneg = min(fneg, i); lneg = i; }
-    }
+    });
     sb = wave_sum(sb);
     sq = wave_sum(sq);
 #pragma unroll
@@ -202,7 +154,7 @@ __global__ __launch_bounds__(kCalThreads) void calibration_kernel(CalArgs A) {
     __syncthreads();
 
     const unsigned Pb = cp[n - 1], Nb = cn[n - 1];
-    for (int w = 0; w < kCalWaves; ++w) {
+    for (int w = 0; w < kBootWaves; ++w) {
       fpos = min(fpos, sc_ix[w][0]); lpos = max(lpos, sc_ix[w][1]);
       fneg = min(fneg, sc_ix[w][2]); lneg = max(lneg, sc_ix[w][3]);
     }
@@ -212,7 +164,7 @@ __global__ __launch_bounds__(kCalThreads) void calibration_kernel(CalArgs A) {
     else if (!(A.l[lpos] < A.l[fneg] && A.l[lneg] < A.l[fpos])) status = 2;
     if (tid == 0) {
       double B2 = 0.0, SP = 0.0;
-      for (int w = 0; w < kCalWaves; ++w) { B2 += sc_bs[w][0]; SP += sc_bs[w][1]; }
+      for (int w = 0; w < kBootWaves; ++w) { B2 += sc_bs[w][0]; SP += sc_bs[w][1]; }
       A.pn[2 * (size_t)bb] = Pb;
       A.pn[2 * (size_t)bb + 1] = Nb;
       A.brier[bb] = B2 / (double)n;
@@ -220,14 +172,14 @@ __global__ __launch_bounds__(kCalThreads) void calibration_kernel(CalArgs A) {
     }
 
     // reliability bins: bin k holds rows [bin_end[k+1], bin_end[k]) of the descending order
-    for (int k = tid; k < K; k += kCalThreads) {
+    for (int k = tid; k < K; k += kBootThreads) {
       const int s = k + 1 < K ? A.bin_end[k + 1] : 0, e = A.bin_end[k];
       const unsigned tp1 = e > 0 ? cp[e - 1] : 0u, fp1 = e > 0 ? cn[e - 1] : 0u;
       const unsigned tp0 = s > 0 ? cp[s - 1] : 0u, fp0 = s > 0 ? cn[s - 1] : 0u;
       A.bin_pos[(size_t)bb * K + k] = tp1 - tp0;
       A.bin_n[(size_t)bb * K + k] = (tp1 - tp0) + (fp1 - fp0);
     }
-    for (int k = wave; k < K; k += kCalWaves) {
+    for (int k = wave; k < K; k += kBootWaves) {
       const int s = k + 1 < K ? A.bin_end[k + 1] : 0, e = A.bin_end[k];
       double acc = 0.0;
       for (int i = s + lane; i < e; i += kWave) {
@@ -238,7 +190,7 @@ __global__ __launch_bounds__(kCalThreads) void calibration_kernel(CalArgs A) {
       if (lane == 0) A.bin_sum_p[(size_t)bb * K + k] = acc;
     }
     // decision curve: rows [0, thr[g]) are treated at t_g
-    for (int g = tid; g < T; g += kCalThreads) {
+    for (int g = tid; g < T; g += kBootThreads) {
       const int k = A.thr[g];
       long long* d = A.dc + 2 * ((size_t)bb * T + g);
       d[0] = k > 0 ? cp[k - 1] : 0u;
@@ -299,44 +251,20 @@ __global__ __launch_bounds__(kCalThreads) void calibration_kernel(CalArgs A) {
 
 void calibration_lds_rows(uintptr_t out) { *reinterpret_cast<long long*>(out) = kCalLdsRows; }
 
-// use_lds: arrays in LDS (n ≤ kCalLdsRows) or in `ws` = [ws_slices][2n] u32, one slice per workgroup.
-// grid ≤ 0 picks one; the results do not depend on it.
+// use_lds, ws, ws_slices and grid: see boot_launch (2 u32 arrays per row)
 void bootstrap_calibration(uintptr_t y, uintptr_t map, uintptr_t p, uintptr_t l, uintptr_t bin_end, uintptr_t thr,
                            long long n, long long p0, int K, int T, long long seed, long long b0, long long nb,
                            int use_lds, uintptr_t ws, long long ws_slices, uintptr_t pn, uintptr_t brier,
                            uintptr_t sum_p, uintptr_t bin_n, uintptr_t bin_pos, uintptr_t bin_sum_p, uintptr_t dc,
                            uintptr_t status, uintptr_t coef, uintptr_t iters, int grid, uintptr_t stream) {
-  HFENS_REQUIRE(n >= 1 && n <= kCalMaxN, "bootstrap_calibration: 1 <= n <= 2^25");
-  HFENS_REQUIRE(p0 >= 1 && p0 <= n, "bootstrap_calibration: first stratum must hold 1..n rows");
   HFENS_REQUIRE(K >= 1 && K <= 64, "bootstrap_calibration: 1 <= bins <= 64");
   HFENS_REQUIRE(T >= 1 && T <= 4096, "bootstrap_calibration: 1 <= thresholds <= 4096");
-  HFENS_REQUIRE(b0 >= 0 && nb >= 0 && b0 + nb <= kCalMaxB, "bootstrap_calibration: replicates must lie in [0, 2^24]");
-  HFENS_REQUIRE(use_lds ? n <= kCalLdsRows : (ws != 0 && ws_slices >= 1),
-                "bootstrap_calibration: n exceeds the LDS path / no global workspace");
-  if (nb == 0) return;
-  int dev = 0, ncu = 256;
-  HFENS_CHECK(hipGetDevice(&dev));
-  HFENS_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  const size_t lds = use_lds ? 8 * (size_t)n : 0;
-  // at most two 1024-thread workgroups are resident on a CU
-  long long cap = use_lds ? (long long)ncu * std::min(2, (int)(kCalLdsPerCu / (lds + kCalStatic)))
-                          : std::min(2LL * ncu, ws_slices);
-  if (grid > 0) cap = use_lds ? grid : std::min((long long)grid, ws_slices);
-  grid = (int)std::min(nb, cap);
   CalArgs A{(const unsigned char*)y, (const int*)map, (const double*)p, (const double*)l, (const int*)bin_end,
             (const int*)thr, (int)n, (int)p0, K, T, (unsigned long long)seed, b0, (int)nb, (unsigned*)ws,
             (long long*)pn, (double*)brier, (double*)sum_p, (long long*)bin_n, (long long*)bin_pos,
             (double*)bin_sum_p, (long long*)dc, (long long*)status, (double*)coef, (long long*)iters};
-  hipStream_t st = as_stream(stream);
-  if (use_lds) {
-    if (lds > 48 * 1024)
-      HFENS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&calibration_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(calibration_kernel<true>, dim3(grid), dim3(kCalThreads), lds, st, A);
-  } else {
-    hipLaunchKernelGGL(calibration_kernel<false>, dim3(grid), dim3(kCalThreads), 0, st, A);
-  }
-  launch_check();
+  boot_launch("bootstrap_calibration", calibration_kernel<true>, calibration_kernel<false>, A, 2, kCalLdsRows,
+              kCalStatic, n, p0, b0, nb, use_lds, ws, ws_slices, grid, stream);
 }
 
 }  // namespace hfens

@@ -125,6 +125,14 @@ __device__ __forceinline__ double wave_max_f64_exact(double x) {
   return __longlong_as_double((long long)k);
 }
 
+// counter-based hash behind the GBDT row bags and the bootstrap draws (ops/reference.py: _splitmix64_t)
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
 __device__ __forceinline__ float fast_exp(float x) {  // e^x via v_exp_f32 (2^x)
   return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
 }

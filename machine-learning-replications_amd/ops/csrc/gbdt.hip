@@ -49,12 +49,6 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
 // Stochastic gradient boosting (subsample < 1): row i of model b is in stage t's bag iff
 // splitmix64(seed_b ⊕ splitmix64(t, global row)) < subsample·2^64 (top 24 bits compared).
 // Counter-based: no RNG state, identical for any launch geometry and any row sharding.
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 __device__ __forceinline__ bool gb_in_bag(unsigned long long seed, int stage, long long gi, unsigned thr24) {
   const unsigned long long k = splitmix64(((unsigned long long)stage << 40) ^ (unsigned long long)gi);
   return (unsigned)(splitmix64(seed ^ k) >> 40) < thr24;

@@ -568,11 +568,15 @@ def stack_oracle(M, X, x3=True):
 
 
 # ---- bootstrap of the held-out metrics ------------------------------------------------------------
-# Resampling law (shared by this mirror, the kernel in csrc/bootstrap.hip and the oracle below):
+# Resampling law (shared by the three mirrors through _resample_counts, the kernels through
+# csrc/resample.h and the oracles through bootstrap_resample):
 # draw j of replicate b over a stratum of m rows is row r of it,
 #     u = splitmix64(seed ^ splitmix64((b << 40) ^ j)),   r = ((u >> 32)·m) >> 32   ∈ [0, m)
 # (bias ≤ m/2^32).  Plain: j ∈ [0, n), m = n.  Stratified: j < P draws the r-th positive (m = P),
 # j ≥ P the r-th negative (m = N), both numbered in original row order.
+
+COMPARE_THREADS = 1024   # kBootThreads and kWave of csrc/resample.h: the f64 folds of the mirrors follow them
+COMPARE_WAVE = 64
 
 def _splitmix64_t(x: torch.Tensor) -> torch.Tensor:
     """splitmix64 on int64 tensors (two's-complement wraparound = mod 2^64)."""
@@ -592,6 +596,89 @@ def _seed_i64(seed: int) -> int:
     return s - (1 << 64) if s >= (1 << 63) else s
 
 
+class _NamedOutputs(tuple):
+    """The outputs of an op in order (``_fields``), also by name."""
+    _fields = ()
+
+    def __new__(cls, *vals):
+        assert len(vals) == len(cls._fields)
+        return super().__new__(cls, vals)
+
+    def __getattr__(self, name):
+        try:
+            return self[self._fields.index(name)]
+        except ValueError:
+            raise AttributeError(name) from None
+
+
+def _tie_groups(ss: torch.Tensor):
+    """For the sorted values ``ss [n]``: every position's first and last position of its run of equal
+    values (int64 ``[n]`` each)."""
+    n, dev = ss.numel(), ss.device
+    start = torch.ones(n, dtype=torch.bool, device=dev)
+    start[1:] = ss[1:] != ss[:-1]
+    firsts = torch.nonzero(start).squeeze(1)
+    gid = torch.cumsum(start.to(torch.int64), 0) - 1
+    lasts = torch.cat([firsts[1:] - 1, torch.tensor([n - 1], device=dev)])
+    return firsts[gid], lasts[gid]
+
+
+def _resample_counts(rowmap, p0: int, n: int, seed: int, b0: int, b1: int, per: int, dev):
+    """The law above, ``per`` replicates at a time: yields ``(bs, cnt)`` with ``bs`` the replicate numbers
+    (int64 ``[Bc]``) and ``cnt [Bc, n]`` (int64) how often each was drawn of the indices ``rowmap[p0·[j ≥ p0]
+    + r]`` (int64 ``[n]``; None: the drawn row itself).  Draws j < p0 take the stratum [0, p0)."""
+    i64 = torch.int64
+    j = torch.arange(n, dtype=i64, device=dev)
+    head = j < p0
+    m = torch.where(head, p0, n - p0)
+    off = torch.where(head, 0, p0)
+    sd = torch.tensor(_seed_i64(seed), dtype=i64, device=dev)
+    for c0 in range(b0, b1, per):
+        bs = torch.arange(c0, min(b1, c0 + per), dtype=i64, device=dev)
+        Bc = bs.numel()
+        u = _splitmix64_t(sd ^ _splitmix64_t((bs[:, None] << 40) ^ j[None, :]))
+        r = (((u >> 32) & 0xFFFFFFFF) * m[None, :]) >> 32
+        at = off[None, :] + r
+        if rowmap is not None:
+            at = rowmap[at]
+        at = at + torch.arange(Bc, device=dev)[:, None] * n
+        yield bs, torch.bincount(at.reshape(-1), minlength=Bc * n).reshape(Bc, n)
+
+
+def _group_ends(gfirst: torch.Tensor, glast: torch.Tensor):
+    """The last position of every tie group ``[E]`` and the group's first position (int64)."""
+    ends = torch.nonzero(glast == torch.arange(glast.numel(), device=glast.device)).squeeze(1)
+    return ends, gfirst[ends]
+
+
+def _rank_stats(cm: torch.Tensor, ys: torch.Tensor, ends: torch.Tensor, f: torch.Tensor, k0: int):
+    """The kernels' rank statistics of the count matrix ``cm [Bc, n]`` in a descending score order with
+    labels ``ys`` and tie groups ``ends``, ``f`` = :func:`_group_ends` (all int64): returns ``Pb``, ``Nb``,
+    ``deg`` (a class missing), the cumulative counts ``TP``, ``FP`` at the group ends ``[Bc, E]``, ``a2``,
+    ``auroc`` and ``ap`` (NaN where ``deg``) and ``conf [Bc, 4]`` = TP FP FN TN of the first ``k0`` rows."""
+    f64 = torch.float64
+    prev = (f - 1).clamp(min=0)
+    cp = torch.cumsum(cm * ys, 1)
+    cn = torch.cumsum(cm * (1 - ys), 1)
+    Pb, Nb = cp[:, -1], cn[:, -1]
+    deg = (Pb == 0) | (Nb == 0)
+    TP, FP = cp[:, ends], cn[:, ends]
+    TP0 = torch.where(f > 0, cp[:, prev], 0)
+    FP0 = torch.where(f > 0, cn[:, prev], 0)
+    a2 = ((FP - FP0) * (TP + TP0)).sum(1)
+    auroc = a2.to(f64) / (2 * Pb * Nb).to(f64)
+    tot = TP + FP
+    term = torch.where(tot > 0, ((TP - TP0) * TP).to(f64) / tot.clamp(min=1).to(f64), 0.0)
+    ap = term.sum(1) / Pb.to(f64)
+    if k0 > 0:
+        tpc, fpc = cp[:, k0 - 1], cn[:, k0 - 1]
+    else:
+        tpc, fpc = torch.zeros_like(Pb), torch.zeros_like(Pb)
+    conf = torch.stack([tpc, fpc, Pb - tpc, Nb - fpc], 1)
+    nan = float("nan")
+    return Pb, Nb, deg, TP, FP, a2, torch.where(deg, nan, auroc), torch.where(deg, nan, ap), conf
+
+
 class BootstrapPlan:
     """What is prepared once per call: the descending stable score order and, in it, the labels
     ``y`` (uint8), every row's tie-group ``gfirst``/``glast`` (int32), ``map`` (int32: drawn row →
@@ -603,19 +690,14 @@ class BootstrapPlan:
         n = score.numel()
         s = score.to(torch.float64)
         order = torch.argsort(s, descending=True, stable=True)
-        ss = s[order]
         pos = y.to(dev) > 0
-        start = torch.ones(n, dtype=torch.bool, device=dev)
-        start[1:] = ss[1:] != ss[:-1]
-        firsts = torch.nonzero(start).squeeze(1)
-        gid = torch.cumsum(start.to(torch.int64), 0) - 1
-        lasts = torch.cat([firsts[1:] - 1, torch.tensor([n - 1], device=dev)])
+        gfirst, glast = _tie_groups(s[order])
         rank = torch.empty(n, dtype=torch.int64, device=dev)
         rank[order] = torch.arange(n, device=dev)
         self.n = n
         self.y = pos[order].to(torch.uint8).contiguous()
-        self.gfirst = firsts[gid].to(torch.int32).contiguous()
-        self.glast = lasts[gid].to(torch.int32).contiguous()
+        self.gfirst = gfirst.to(torch.int32).contiguous()
+        self.glast = glast.to(torch.int32).contiguous()
         self.P = int(pos.sum())
         if stratified:
             self.map = torch.cat([rank[pos], rank[~pos]]).to(torch.int32).contiguous()
@@ -641,47 +723,16 @@ def bootstrap_metrics(y: torch.Tensor, score: torch.Tensor, n_boot: int, *, seed
     b1 = n_boot if b1 is None else b1
     i64, f64 = torch.int64, torch.float64
     ys = pl.y.to(i64)
-    rows = torch.arange(n, device=dev)
-    ends = torch.nonzero(pl.glast.to(i64) == rows).squeeze(1)          # last row of every tie group
-    f = pl.gfirst.to(i64)[ends]
-    prev = (f - 1).clamp(min=0)
-    E = ends.numel()
-    j = torch.arange(n, dtype=i64, device=dev)
-    head = j < pl.p0
-    m = torch.where(head, pl.p0, n - pl.p0)
-    off = torch.where(head, 0, pl.p0)
-    sd = torch.tensor(_seed_i64(seed), dtype=i64, device=dev)
+    ends, f = _group_ends(pl.gfirst.to(i64), pl.glast.to(i64))
     g = torch.arange(G, dtype=i64, device=dev)
     G1 = G - 1
     nan = float("nan")
     outs = [[] for _ in range(6)]
-    per = max(1, chunk_elems // n)
-    for c0 in range(b0, b1, per):
-        bs = torch.arange(c0, min(b1, c0 + per), dtype=i64, device=dev)
-        Bc = bs.numel()
-        u = _splitmix64_t(sd ^ _splitmix64_t((bs[:, None] << 40) ^ j[None, :]))
-        r = (((u >> 32) & 0xFFFFFFFF) * m[None, :]) >> 32
-        at = pl.map.to(i64)[off[None, :] + r] + torch.arange(Bc, device=dev)[:, None] * n
-        cnt = torch.bincount(at.reshape(-1), minlength=Bc * n).reshape(Bc, n)
-        cp = torch.cumsum(cnt * ys, 1)
-        cn = torch.cumsum(cnt * (1 - ys), 1)
-        Pb, Nb = cp[:, -1], cn[:, -1]
-        deg = (Pb == 0) | (Nb == 0)
-        TP, FP = cp[:, ends], cn[:, ends]
-        TP0 = torch.where(f > 0, cp[:, prev], 0)
-        FP0 = torch.where(f > 0, cn[:, prev], 0)
-        a2 = ((FP - FP0) * (TP + TP0)).sum(1)
-        auroc = a2.to(f64) / (2 * Pb * Nb).to(f64)
-        tot = TP + FP
-        term = torch.where(tot > 0, ((TP - TP0) * TP).to(f64) / tot.clamp(min=1).to(f64), 0.0)
-        ap = term.sum(1) / Pb.to(f64)
-        if pl.k0 > 0:
-            tpc, fpc = cp[:, pl.k0 - 1], cn[:, pl.k0 - 1]
-        else:
-            tpc, fpc = torch.zeros_like(Pb), torch.zeros_like(Pb)
-        conf = torch.stack([tpc, fpc, Pb - tpc, Nb - fpc], 1)
+    for bs, cnt in _resample_counts(pl.map.to(i64), pl.p0, n, seed, b0, b1, max(1, chunk_elems // n), dev):
+        Pb, Nb, deg, TP, FP, a2, auroc, ap, conf = _rank_stats(cnt, ys, ends, f, pl.k0)
         # ROC vertices: (0, 0), then the tie-group ends
-        z = torch.zeros(Bc, 1, dtype=i64, device=dev)
+        E = TP.shape[1]
+        z = torch.zeros(bs.numel(), 1, dtype=i64, device=dev)
         V, T = torch.cat([z, FP], 1), torch.cat([z, TP], 1)
         bound = g[None, :] * Nb[:, None]
         ks = torch.searchsorted((V * G1).contiguous(), bound.contiguous(), right=True) - 1
@@ -694,8 +745,6 @@ def bootstrap_metrics(y: torch.Tensor, score: torch.Tensor, n_boot: int, *, seed
         frac = num.to(f64) / den.to(f64)
         pbf = Pb.to(f64)[:, None]
         tpr = torch.where(exact, tk.to(f64) / pbf, (tk.to(f64) + (t1 - tk).to(f64) * frac) / pbf)
-        auroc = torch.where(deg, nan, auroc)
-        ap = torch.where(deg, nan, ap)
         tpr = torch.where(deg[:, None], nan, tpr)
         for o, v in zip(outs, (auroc, ap, a2, torch.stack([Pb, Nb], 1), conf, tpr)):
             o.append(v)
@@ -796,7 +845,7 @@ def bootstrap_oracle(y, score, n_boot: int, *, seed: int = 0, stratified: bool =
 
 
 # ---- bootstrap of the calibration and decision-curve statistics --------------------------------------
-# Same resampling law as above (csrc/calibration.hip draws what csrc/bootstrap.hip draws).  Definitions
+# Same resampling law as above (_resample_counts here, csrc/resample.h in the kernels).  Definitions
 # shared by the kernel, this mirror and the oracle:
 #   bin of p     = #{k ∈ 1..K−1 : p ≥ k/K}, k/K the f64 quotient, compared in f64 (0.3 is in [0.3, 0.4));
 #   treated at t = p ≥ t, thresholds t_g = g/(T+1), g = 1..T, the f64 quotient;
@@ -815,19 +864,9 @@ CAL_MAX_ITER = 50
 CAL_MAX_HALVE = 40
 
 
-class CalibrationBootstrap(tuple):
+class CalibrationBootstrap(_NamedOutputs):
     """The outputs of ``bootstrap_calibration`` in order, also by name."""
     _fields = ("pn", "brier", "sum_p", "bin_n", "bin_pos", "bin_sum_p", "dc", "status", "coef", "iters")
-
-    def __new__(cls, *vals):
-        assert len(vals) == len(cls._fields)
-        return super().__new__(cls, vals)
-
-    def __getattr__(self, name):
-        try:
-            return self[self._fields.index(name)]
-        except ValueError:
-            raise AttributeError(name) from None
 
 
 class CalibrationPlan(BootstrapPlan):
@@ -972,20 +1011,8 @@ def bootstrap_calibration(y: torch.Tensor, score: torch.Tensor, n_boot: int, *, 
     n, K, T = pl.n, pl.K, pl.T
     b1 = n_boot if b1 is None else b1
     i64, f64 = torch.int64, torch.float64
-    j = torch.arange(n, dtype=i64, device=dev)
-    head = j < pl.p0
-    m = torch.where(head, pl.p0, n - pl.p0)
-    off = torch.where(head, 0, pl.p0)
-    sd = torch.tensor(_seed_i64(seed), dtype=i64, device=dev)
     outs = [[] for _ in range(10)]
-    per = max(1, chunk_elems // n)
-    for c0 in range(b0, b1, per):
-        bs = torch.arange(c0, min(b1, c0 + per), dtype=i64, device=dev)
-        Bc = bs.numel()
-        u = _splitmix64_t(sd ^ _splitmix64_t((bs[:, None] << 40) ^ j[None, :]))
-        r = (((u >> 32) & 0xFFFFFFFF) * m[None, :]) >> 32
-        at = pl.map.to(i64)[off[None, :] + r] + torch.arange(Bc, device=dev)[:, None] * n
-        cnt = torch.bincount(at.reshape(-1), minlength=Bc * n).reshape(Bc, n)
+    for _, cnt in _resample_counts(pl.map.to(i64), pl.p0, n, seed, b0, b1, max(1, chunk_elems // n), dev):
         for o, v in zip(outs, _cal_stats(pl, cnt)):
             o.append(v)
     if not outs[0]:
@@ -1094,7 +1121,7 @@ def calibration_oracle(y, score, n_boot: int, *, seed: int = 0, stratified: bool
 
 
 # ---- paired bootstrap comparison of score columns -----------------------------------------------------
-# Same resampling law again (csrc/compare.hip draws what csrc/bootstrap.hip draws), the rows drawn ONCE
+# Same resampling law again (_resample_counts here, csrc/resample.h in the kernels), the rows drawn ONCE
 # per replicate and every column scored on them.  Column 0 is the reference model.  Definitions shared
 # by the kernel, this mirror and the oracle, with hi_m = score_m > threshold:
 #   reclass[m] = (eu, ed, nu, nd): drawn events with hi_0 = 1, hi_m = 0 (the reference moves the event
@@ -1103,23 +1130,10 @@ def calibration_oracle(y, score, n_boot: int, *, seed: int = 0, stratified: bool
 #                original row order: thread t of 1024 over rows [t·chunk, (t+1)·chunk), chunk =
 #                ceil(n/1024), then the 64 lanes of a wave by an xor tree, then the 16 waves in order.
 
-COMPARE_THREADS = 1024
-COMPARE_WAVE = 64
 
-
-class CompareBootstrap(tuple):
+class CompareBootstrap(_NamedOutputs):
     """The outputs of ``bootstrap_compare`` in order, also by name."""
     _fields = ("auroc", "ap", "a2", "pn", "conf", "reclass", "sums")
-
-    def __new__(cls, *vals):
-        assert len(vals) == len(cls._fields)
-        return super().__new__(cls, vals)
-
-    def __getattr__(self, name):
-        try:
-            return self[self._fields.index(name)]
-        except ValueError:
-            raise AttributeError(name) from None
 
 
 class ComparePlan:
@@ -1139,16 +1153,11 @@ class ComparePlan:
         order, ys, gf, gl = [], [], [], []
         for m in range(M):
             o = torch.argsort(s[m], descending=True, stable=True)
-            ss = s[m][o]
-            start = torch.ones(n, dtype=torch.bool, device=dev)
-            start[1:] = ss[1:] != ss[:-1]
-            firsts = torch.nonzero(start).squeeze(1)
-            gid = torch.cumsum(start.to(torch.int64), 0) - 1
-            lasts = torch.cat([firsts[1:] - 1, torch.tensor([n - 1], device=dev)])
+            gfirst, glast = _tie_groups(s[m][o])
             order.append(o)
             ys.append(pos[o])
-            gf.append(firsts[gid])
-            gl.append(lasts[gid])
+            gf.append(gfirst)
+            gl.append(glast)
         self.n, self.M = n, M
         self.y = pos.to(torch.uint8).contiguous()
         self.p = s
@@ -1205,53 +1214,20 @@ def bootstrap_compare(y: torch.Tensor, scores: torch.Tensor, n_boot: int, *, see
     n, M = pl.n, pl.M
     b1 = n_boot if b1 is None else b1
     i64, f64 = torch.int64, torch.float64
-    rows = torch.arange(n, device=dev)
-    j = torch.arange(n, dtype=i64, device=dev)
-    head = j < pl.p0
-    mm = torch.where(head, pl.p0, n - pl.p0)
-    off = torch.where(head, 0, pl.p0)
-    rowmap = pl.rowmap.to(i64) if pl.rowmap is not None else rows
-    sd = torch.tensor(_seed_i64(seed), dtype=i64, device=dev)
+    rowmap = pl.rowmap.to(i64) if pl.rowmap is not None else None
     yb = pl.y > 0
     yf = pl.y.to(f64)
     hi = pl.hi > 0
     k0 = pl.k0.tolist()
-    nan = float("nan")
+    groups = [_group_ends(pl.gfirst[m].to(i64), pl.glast[m].to(i64)) for m in range(M)]
     outs = [[] for _ in range(7)]
-    per = max(1, chunk_elems // n)
-    for c0 in range(b0, b1, per):
-        bs = torch.arange(c0, min(b1, c0 + per), dtype=i64, device=dev)
-        Bc = bs.numel()
-        u = _splitmix64_t(sd ^ _splitmix64_t((bs[:, None] << 40) ^ j[None, :]))
-        r = (((u >> 32) & 0xFFFFFFFF) * mm[None, :]) >> 32
-        at = rowmap[off[None, :] + r] + torch.arange(Bc, device=dev)[:, None] * n
-        cnt = torch.bincount(at.reshape(-1), minlength=Bc * n).reshape(Bc, n)
+    for _, cnt in _resample_counts(rowmap, pl.p0, n, seed, b0, b1, max(1, chunk_elems // n), dev):
         C = cnt.to(f64)
         cols = [[] for _ in range(6)]
         pn = None
         for m in range(M):
-            o = pl.order[m].to(i64)
-            ys = pl.ys[m].to(i64)
-            ends = torch.nonzero(pl.glast[m].to(i64) == rows).squeeze(1)
-            f = pl.gfirst[m].to(i64)[ends]
-            prev = (f - 1).clamp(min=0)
-            cm = cnt[:, o]
-            cp = torch.cumsum(cm * ys, 1)
-            cn = torch.cumsum(cm * (1 - ys), 1)
-            Pb, Nb = cp[:, -1], cn[:, -1]
-            deg = (Pb == 0) | (Nb == 0)
-            TP, FP = cp[:, ends], cn[:, ends]
-            TP0 = torch.where(f > 0, cp[:, prev], 0)
-            FP0 = torch.where(f > 0, cn[:, prev], 0)
-            a2 = ((FP - FP0) * (TP + TP0)).sum(1)
-            auroc = a2.to(f64) / (2 * Pb * Nb).to(f64)
-            tot = TP + FP
-            term = torch.where(tot > 0, ((TP - TP0) * TP).to(f64) / tot.clamp(min=1).to(f64), 0.0)
-            ap = term.sum(1) / Pb.to(f64)
-            if k0[m] > 0:
-                tpc, fpc = cp[:, k0[m] - 1], cn[:, k0[m] - 1]
-            else:
-                tpc, fpc = torch.zeros_like(Pb), torch.zeros_like(Pb)
+            Pb, Nb, _, _, _, a2, auroc, ap, conf = _rank_stats(cnt[:, pl.order[m].to(i64)], pl.ys[m].to(i64),
+                                                               *groups[m], k0[m])
             if m == 0:
                 pn = torch.stack([Pb, Nb], 1)
             up, down = hi[0] & ~hi[m], ~hi[0] & hi[m]
@@ -1262,8 +1238,7 @@ def bootstrap_compare(y: torch.Tensor, scores: torch.Tensor, n_boot: int, *, see
             sm = torch.stack([_compare_fold(torch.where(yb[None, :], cpm, 0.0)),
                               _compare_fold(torch.where(yb[None, :], 0.0, cpm)),
                               _compare_fold(C * (d * d)[None, :])], 1)
-            for o_, v in zip(cols, (torch.where(deg, nan, auroc), torch.where(deg, nan, ap), a2,
-                                    torch.stack([tpc, fpc, Pb - tpc, Nb - fpc], 1), rc, sm)):
+            for o_, v in zip(cols, (auroc, ap, a2, conf, rc, sm)):
                 o_.append(v)
         au, ap_, a2_, cf, rc_, sm_ = (torch.stack(c, 1) for c in cols)
         for o_, v in zip(outs, (au, ap_, a2_, pn, cf, rc_, sm_)):

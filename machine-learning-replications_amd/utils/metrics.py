@@ -187,6 +187,28 @@ def evaluate(y_true, proba1) -> Dict[str, float]:
             "accuracy": (tp + tn) / max(1, tp + tn + fp + fn), "tp": tp, "fp": fp, "tn": tn, "fn": fn}
 
 
+def _percentile_bounds(v: np.ndarray, qs):
+    """``lo, hi, se`` of the replicate values ``v`` (NaN: replicate left out): the quantiles ``qs`` by
+    linear interpolation and the standard deviation (ddof 1); NaN without enough replicates."""
+    nan = float("nan")
+    ok = v[~np.isnan(v)]
+    lo, hi = np.quantile(ok, qs) if ok.size else (nan, nan)
+    return float(lo), float(hi), float(np.std(ok, ddof=1)) if ok.size > 1 else nan
+
+
+def _ci_inputs(name: str, y_true, proba1, alpha: float, device):
+    """Labels and scores as flat tensors on ``device`` (default: where the scores live), scores floating."""
+    y = _t(y_true).reshape(-1)
+    p = _t(proba1).reshape(-1)
+    dev = torch.device(device) if device is not None else p.device
+    y, p = y.to(dev), p.to(dev)
+    if not p.is_floating_point():
+        p = p.to(torch.float64)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"{name}: alpha = {alpha} outside (0, 1)")
+    return y, p
+
+
 def bootstrap_ci(y_true, proba1, n_boot: int = 2000, seed: int = 2020, alpha: float = 0.05,
                  stratified: bool = False, threshold: float = 0.5, device=None) -> Dict[str, object]:
     """Nonparametric bootstrap of the held-out rows: ``n_boot`` resamples with replacement
@@ -203,14 +225,7 @@ def bootstrap_ci(y_true, proba1, n_boot: int = 2000, seed: int = 2020, alpha: fl
     ``tpr_median`` / ``tpr_hi`` are the pointwise band of the replicates' ROC curves.  All values
     are Python floats and lists."""
     from .. import ops
-    y = _t(y_true).reshape(-1)
-    p = _t(proba1).reshape(-1)
-    dev = torch.device(device) if device is not None else p.device
-    y, p = y.to(dev), p.to(dev)
-    if not p.is_floating_point():
-        p = p.to(torch.float64)
-    if not 0.0 < alpha < 1.0:
-        raise ValueError(f"bootstrap_ci: alpha = {alpha} outside (0, 1)")
+    y, p = _ci_inputs("bootstrap_ci", y_true, proba1, alpha, device)
     auroc, ap, _, pn, conf, tpr = ops.bootstrap_metrics(y, p, n_boot, seed=seed, stratified=stratified,
                                                         threshold=threshold)
     auroc, ap, tpr = auroc.cpu().numpy(), ap.cpu().numpy(), tpr.cpu().numpy()
@@ -234,11 +249,8 @@ def bootstrap_ci(y_true, proba1, n_boot: int = 2000, seed: int = 2020, alpha: fl
                               "stratified": bool(stratified), "threshold": float(threshold),
                               "n_degenerate": int(deg.sum())}
     for k, v in reps.items():
-        v = np.where(deg, np.nan, v)
-        ok = v[~np.isnan(v)]
-        lo, hi = (np.quantile(ok, qs) if ok.size else (float("nan"), float("nan")))
-        out[k] = {"point": float(point[k]), "lo": float(lo), "hi": float(hi),
-                  "se": float(np.std(ok, ddof=1)) if ok.size > 1 else float("nan")}
+        lo, hi, se = _percentile_bounds(np.where(deg, np.nan, v), qs)
+        out[k] = {"point": float(point[k]), "lo": lo, "hi": hi, "se": se}
     G = tpr.shape[1]
     keep = tpr[~deg]
     band = np.quantile(keep, [qs[0], 0.5, qs[1]], axis=0) if keep.shape[0] else np.full((3, G), np.nan)
@@ -265,14 +277,7 @@ def calibration_ci(y_true, proba1, n_boot: int = 2000, seed: int = 2020, alpha: 
     the slope and intercept quantiles only.  ``n_boot = 0`` gives the points with NaN bounds."""
     from .. import ops
     from ..ops import reference as ref
-    y = _t(y_true).reshape(-1)
-    p = _t(proba1).reshape(-1)
-    dev = torch.device(device) if device is not None else p.device
-    y, p = y.to(dev), p.to(dev)
-    if not p.is_floating_point():
-        p = p.to(torch.float64)
-    if not 0.0 < alpha < 1.0:
-        raise ValueError(f"calibration_ci: alpha = {alpha} outside (0, 1)")
+    y, p = _ci_inputs("calibration_ci", y_true, proba1, alpha, device)
     n_boot = int(n_boot)
     if n_boot < 0:
         raise ValueError(f"calibration_ci: n_boot = {n_boot} is negative")
@@ -299,25 +304,19 @@ def calibration_ci(y_true, proba1, n_boot: int = 2000, seed: int = 2020, alpha: 
                 "nb": dc[..., 0] / n - (dc[..., 1] / n) * odds}
     point, reps = derive(pt), derive(r)
     qs = [alpha / 2, 1 - alpha / 2]
-    nan = float("nan")
-
-    def bounds(v):
-        ok = v[~np.isnan(v)]
-        lo, hi = np.quantile(ok, qs) if ok.size else (nan, nan)
-        return float(lo), float(hi), float(np.std(ok, ddof=1)) if ok.size > 1 else nan
     out: Dict[str, object] = {"n_boot": n_boot, "seed": int(seed), "alpha": float(alpha),
                               "stratified": bool(stratified), "bins": int(bins),
                               "n_degenerate": int((r["status"] == 1).sum()),
                               "n_separable": int((r["status"] == 2).sum()),
                               "n_unconverged": int((r["status"] == 3).sum())}
     for k in ("brier", "oe_ratio", "intercept", "slope", "ece"):
-        lo, hi, se = bounds(reps[k])
+        lo, hi, se = _percentile_bounds(reps[k], qs)
         out[k] = {"point": float(point[k]), "lo": lo, "hi": hi, "se": se}
-    ob = [bounds(reps["obs"][:, k]) for k in range(int(bins))]
+    ob = [_percentile_bounds(reps["obs"][:, k], qs) for k in range(int(bins))]
     out["reliability"] = {"pred_mean": [float(v) for v in point["pred"]], "obs": [float(v) for v in point["obs"]],
                           "obs_lo": [b[0] for b in ob], "obs_hi": [b[1] for b in ob],
                           "count": [int(v) for v in pt["bin_n"]]}
-    nbq = [bounds(reps["nb"][:, g]) for g in range(t.size)]
+    nbq = [_percentile_bounds(reps["nb"][:, g], qs) for g in range(t.size)]
     P0, N0 = pt["pn"]
     out["decision_curve"] = {"thresholds": t.tolist(), "net_benefit": point["nb"].tolist(),
                              "net_benefit_lo": [b[0] for b in nbq], "net_benefit_hi": [b[1] for b in nbq],
@@ -465,12 +464,11 @@ def compare_ci(y_true, scores: Dict[str, object], reference: str, n_boot: int = 
                 cmp[k] = None
                 continue
             v = np.where(deg, np.nan, reps[k])
+            lo, hi_, se = _percentile_bounds(v, qs)
             ok = v[~np.isnan(v)]
-            lo, hi_ = np.quantile(ok, qs) if ok.size else (nan, nan)
             p = min(1.0, 2.0 * min(int((ok <= 0).sum()) + 1, int((ok >= 0).sum()) + 1) / (ok.size + 1)) \
                 if ok.size else nan
-            cmp[k] = {"point": float(point[k][0]), "lo": float(lo), "hi": float(hi_),
-                      "se": float(np.std(ok, ddof=1)) if ok.size > 1 else nan, "p": float(p)}
+            cmp[k] = {"point": float(point[k][0]), "lo": lo, "hi": hi_, "se": se, "p": float(p)}
         cmp["delong"] = delong_test(yh, Sh[0], Sh[m])
         out["comparisons"][names[m]] = cmp
     return out
