@@ -61,7 +61,9 @@ def _newton_finish(Hb, gb, wb, pn, lam, d, eps_diag):
     return un - wb if ok else None
 
 
-def _host_l1_qp(H, g, w, penal, lam, max_sweeps=200, tol=1e-12, eps_diag=0.0):
+def _host_l1_qp(H, g, w, penal, lam, max_sweeps=200, tol=1e-12, eps_diag=0.0, capped=None):
+    """``capped``: an optional list that receives, per model, whether the solve ran into
+    ``max_sweeps`` (left by neither the step rule nor the exact finish)."""
     Hn, gn, wn = H.cpu().numpy(), g.cpu().numpy(), w.cpu().numpy()
     pn = penal.cpu().numpy().astype(bool)
     B, F1 = gn.shape
@@ -70,6 +72,8 @@ def _host_l1_qp(H, g, w, penal, lam, max_sweeps=200, tol=1e-12, eps_diag=0.0):
         Hb, gb, wb = Hn[b], gn[b], wn[b]
         d = np.zeros(F1)
         Hd = np.zeros(F1)
+        if capped is not None:
+            capped.append(True)
         for sweep in range(max_sweeps):
             mx = 0.0
             for k in range(F1):
@@ -87,13 +91,16 @@ def _host_l1_qp(H, g, w, penal, lam, max_sweeps=200, tol=1e-12, eps_diag=0.0):
                     Hd += Hb[:, k] * step
                     d[k] = nd
                     mx = max(mx, abs(step))
-            if mx <= tol:
-                break
-            if sweep % 4 == 3:   # ops/csrc/l1qp.h: exact finish on the sign pattern, if optimal
+            left = mx <= tol
+            if not left and sweep % 4 == 3:   # ops/csrc/l1qp.h: exact finish on the sign pattern, if optimal
                 dn = _newton_finish(Hb, gb, wb, pn, lam, d, eps_diag)
                 if dn is not None:
                     d = dn
-                    break
+                    left = True
+            if left:
+                if capped is not None:
+                    capped[-1] = False
+                break
         out[b] = d
     return torch.as_tensor(out, dtype=g.dtype, device=g.device)
 
@@ -434,7 +441,6 @@ def launch_logreg_batch(models, X: torch.Tensor, y: torch.Tensor, masks: Optiona
     penal = torch.ones(F1, dtype=torch.uint8, device=dev)
     if not l1 and m0.fit_intercept:
         penal[-1:].zero_()  # lbfgs path: intercept not penalised (a fill: no host→device copy)
-    pen_f = penal.to(torch.float64)
     scale = float(m0.intercept_scaling) if (m0.fit_intercept and l1) else 1.0
     if fused:
         LAST_PATH["path"] = "fused"
@@ -442,6 +448,19 @@ def launch_logreg_batch(models, X: torch.Tensor, y: torch.Tensor, masks: Optiona
         return dict(models=models, F=F, scale=scale, fit_intercept=bool(m0.fit_intercept), dev=dev,
                     fused=_launch_fused(Xa, s, ypm, penal, C, l1, max_outer, flags))
     LAST_PATH["path"] = "loop"
+    W, n_iter = _solve_loop(Xa, s, ypm, penal, C, l1, max_outer, group)
+    for b, m in enumerate(models):
+        coef = W[b, :F]
+        intercept = W[b, F] * scale if m0.fit_intercept else torch.zeros((), dtype=torch.float64, device=dev)
+        m.set_fitted(coef, intercept.reshape(1), [n_iter], F, device=dev)
+    return dict(models=models)
+
+
+def _solve_loop(Xa, s, ypm, penal, C: float, l1: bool, max_outer: int, group=None):
+    """The host-driven solve of B models (the arguments of :func:`_launch_fused`): returns
+    (W [B, F1], outer iterations).  The batch stops when every model has converged."""
+    B, F1, dev = s.shape[0], Xa.shape[1], Xa.device
+    pen_f = penal.to(torch.float64)
     W = torch.zeros(B, F1, dtype=torch.float64, device=dev)
     alphas = 0.5 ** torch.arange(8, dtype=torch.float64, device=dev)
 
@@ -469,16 +488,17 @@ def launch_logreg_batch(models, X: torch.Tensor, y: torch.Tensor, masks: Optiona
         data0 = C * (s.t() * torch.nn.functional.softplus(-M)).sum(0)
         grad, H, data0 = _allreduce([grad, H, data0], group)
         if l1:
-            # min-norm subgradient for the stopping rule
+            # min-norm subgradient for the stopping rule (an unpenalised coordinate: its gradient)
             sub = torch.where(W != 0, grad + torch.sign(W),
                               torch.sign(grad) * (grad.abs() - 1.0).clamp(min=0.0))
+            sub = torch.where(penal.bool()[None], sub, grad)
             gn = sub.abs().sum(1)
             if g0norm is None:
                 g0norm = gn.clamp(min=1e-300)
             if bool((gn <= 1e-9 * g0norm).all()):
                 break
             Hr = H + 1e-12 * torch.eye(F1, dtype=torch.float64, device=dev)
-            if X.is_cuda:
+            if Xa.is_cuda:
                 E = ops.ext()
                 d = torch.empty_like(W)
                 E.l1_qp_cd(B, F1, Hr.contiguous().data_ptr(), grad.contiguous().data_ptr(),
@@ -486,7 +506,7 @@ def launch_logreg_batch(models, X: torch.Tensor, y: torch.Tensor, masks: Optiona
                            d.data_ptr(), ops.stream_ptr(dev))
             else:
                 d = _host_l1_qp(Hr, grad, W, penal, 1.0)
-            delta = (grad * d).sum(1) + (W + d).abs().sum(1) - W.abs().sum(1)
+            delta = (grad * d).sum(1) + ((W + d).abs() * pen_f).sum(1) - (W.abs() * pen_f).sum(1)
         else:
             gfull = grad + W * pen_f
             if g0norm is None:
@@ -516,8 +536,4 @@ def launch_logreg_batch(models, X: torch.Tensor, y: torch.Tensor, masks: Optiona
         Z = Z + a[None, :] * Xd
         if bool(((a[:, None] * d).abs().max(1).values <= 1e-14 * (1 + W.abs().max(1).values)).all()):
             break
-    for b, m in enumerate(models):
-        coef = W[b, :F]
-        intercept = W[b, F] * scale if m0.fit_intercept else torch.zeros((), dtype=torch.float64, device=dev)
-        m.set_fitted(coef, intercept.reshape(1), [n_iter], F, device=dev)
-    return dict(models=models)
+    return W, n_iter

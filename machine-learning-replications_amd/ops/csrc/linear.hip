@@ -164,7 +164,8 @@ __global__ __launch_bounds__(64) void lasso_cd_path_kernel(int F, int A, const d
       }
     }
     if (j < F) coefs[((size_t)p * A + a) * F + j] = wj;
-    if (j == 0) { gaps[p * A + a] = gap; iters[p * A + a] = it + 1; }
+    // sweeps run: a path that runs out of sweeps leaves the loop with it == max_iter
+    if (j == 0) { gaps[p * A + a] = gap; iters[p * A + a] = min(it + 1, max_iter); }
   }
 }
 

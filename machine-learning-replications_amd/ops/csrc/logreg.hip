@@ -258,8 +258,10 @@ __global__ __launch_bounds__(kLrThreads) void logreg_fused_kernel(LrJob J) {
       if (wave == 0) {
         const int j = lane;
         const double gj = j < F1 ? gr[j] : 0.0, wj = j < F1 ? Wl[j] : 0.0;
-        double sub = 0.0;   // min-norm subgradient of g·w + ‖w‖₁
-        if (j < F1)
+        const bool pen_j = j < F1 && J.penal[j];
+        double sub = 0.0;   // min-norm subgradient of g·w + Σ_pen |w_j| (an unpenalised coordinate: g_j)
+        if (j < F1 && !pen_j) sub = gj;
+        else if (j < F1)
           sub = wj != 0.0 ? gj + (wj > 0.0 ? 1.0 : -1.0)
                           : (gj > 0.0 ? 1.0 : (gj < 0.0 ? -1.0 : 0.0)) * fmax(fabs(gj) - 1.0, 0.0);
         const double gn = wave_sum(fabs(sub));
@@ -303,7 +305,8 @@ __global__ __launch_bounds__(kLrThreads) void logreg_fused_kernel(LrJob J) {
               break;
           }
         }
-        const double delta = wave_sum(j < F1 ? gj * dj + fabs(wj + dj) - fabs(wj) : 0.0);
+        // predicted decrease gᵀd + Σ_pen (|w_j + d_j| − |w_j|): the penalty counts penalised coordinates only
+        const double delta = wave_sum(pen_j ? gj * dj + fabs(wj + dj) - fabs(wj) : (j < F1 ? gj * dj : 0.0));
         const double reg0 = wave_sum((j < F1 && J.penal[j]) ? fabs(wj) : 0.0);
         if (j < F1) dd[j] = dj;
         if (lane == 0) { sc[0] = stop ? 1.0 : 0.0; sc[1] = delta; sc[2] = reg0; }

@@ -1574,3 +1574,174 @@ def ws_select_oracle(alpha, G, npos, Cp, Cn, Q, prev, key_bits=WS_KEY_BITS):
     taken[pl] = True
     prev = np.asarray(prev, dtype=np.int64)
     return pu, pl, prev[~taken[prev]] if prev.size else e
+
+
+# ----------------------------------------------------------------------------- linear-model certificates
+# numpy longdouble, written from the objectives themselves (liblinear's L1 / lbfgs's L2 logistic
+# objective, newGLMNET's quadratic subproblem, sklearn's Gram-form lasso duality gap), with the f64
+# arrays a kernel receives taken as exact.  A convex optimum needs no second solver: the min-norm
+# subgradient or the duality gap at the kernel's own answer certifies it however it was reached.
+# Nothing here imports torch, models/logreg_solver.py or models/lasso.py.
+def _ld(a):
+    np = _np()
+    return np.asarray(a, dtype=np.float64).astype(np.longdouble)
+
+
+def _lm_softplus(x):
+    """log(1 + e^x) without overflow: max(x, 0) + log1p(e^−|x|)."""
+    np = _np()
+    return np.maximum(x, 0) + np.log1p(np.exp(-np.abs(x)))
+
+
+def _lm_sigmoid(x):
+    """1 / (1 + e^−x) without overflow (e^x / (1 + e^x) for x < 0)."""
+    np = _np()
+    e = np.exp(-np.abs(x))
+    return np.where(x >= 0, 1 / (1 + e), e / (1 + e))
+
+
+def logreg_objective(Xa, s, ypm, w, C, l1, penal):
+    """``C·Σ_r s_r·softplus(−y_r·x̃_r·w) + Σ_{j penalised} |w_j|`` (``l1``) or ``½ w_j²``."""
+    np = _np()
+    Xa, s, y, w = _ld(Xa), _ld(s), _ld(ypm), _ld(w)
+    pen = np.asarray(penal).astype(bool)
+    data = np.longdouble(C) * (s * _lm_softplus(-y * (Xa @ w))).sum()
+    return data + (np.abs(w[pen]).sum() if l1 else (w[pen] * w[pen]).sum() / 2)
+
+
+def _logreg_grad(Xa, s, y, w, C):
+    # d/dw C·Σ s·softplus(−y z) = −C·Σ s·y·σ(−y z)·x̃
+    return _np().longdouble(C) * ((-(s * y * _lm_sigmoid(-y * (Xa @ w)))) @ Xa)
+
+
+def _min_norm_subgradient(g, w, pen, l1):
+    np = _np()
+    if not l1:
+        return np.where(pen, g + w, g)
+    at0 = np.sign(g) * np.maximum(np.abs(g) - 1, 0)
+    return np.where(pen, np.where(w != 0, g + np.sign(w), at0), g)
+
+
+def logreg_kkt(Xa, s, ypm, w, C, l1, penal):
+    """The 1-norm of the min-norm subgradient of :func:`logreg_objective` at ``w``, with g the
+    gradient of the data term: L1 and penalised, g_j + sign(w_j) where w_j ≠ 0 and
+    sign(g_j)·max(|g_j| − 1, 0) where w_j = 0; L2 and penalised, g_j + w_j; unpenalised, g_j.
+    Returns ``{"norm", "norm0", "ratio"}``: the norm at w, at w = 0, and norm / norm0 (the solvers'
+    relative stopping measure; 0 when w = 0 is itself optimal and the norm at w is 0)."""
+    np = _np()
+    Xa, s, y, w = _ld(Xa), _ld(s), _ld(ypm), _ld(w)
+    pen = np.asarray(penal).astype(bool)
+    norm = np.abs(_min_norm_subgradient(_logreg_grad(Xa, s, y, w, C), w, pen, l1)).sum()
+    w0 = np.zeros_like(w)
+    norm0 = np.abs(_min_norm_subgradient(_logreg_grad(Xa, s, y, w0, C), w0, pen, l1)).sum()
+    ratio = norm / norm0 if norm0 > 0 else (np.longdouble(0) if norm == 0 else np.longdouble(np.inf))
+    return {"norm": norm, "norm0": norm0, "ratio": ratio}
+
+
+def _ld_solve(A, b):
+    """A x = b in longdouble by Gaussian elimination with partial pivoting (numpy's LAPACK front end
+    has no longdouble)."""
+    np = _np()
+    A = np.array(A, dtype=np.longdouble)
+    x = np.array(b, dtype=np.longdouble)
+    m = A.shape[0]
+    for k in range(m):
+        p = k + int(np.argmax(np.abs(A[k:, k])))
+        if p != k:
+            A[[k, p]] = A[[p, k]]
+            x[[k, p]] = x[[p, k]]
+        f = A[k + 1:, k] / A[k, k]
+        A[k + 1:, k:] -= f[:, None] * A[k, k:][None, :]
+        x[k + 1:] -= f * x[k]
+    for k in range(m - 1, -1, -1):
+        x[k] = (x[k] - A[k, k + 1:] @ x[k + 1:]) / A[k, k]
+    return x
+
+
+def logreg_newton_step(Xa, s, ypm, C, penal):
+    """The first damped-Newton step of the L2 objective from w = 0, exactly.  At w = 0 every σ is ½:
+    g = −½·C·Σ s·y·x̃, H = ¼·C·X̃ᵀ diag(s) X̃, and the direction is d = −(H + diag(pen))⁻¹ g.
+    Returns a dict: ``d``, ``A`` (= H + diag(pen)), ``g``, ``F0``, ``delta`` (= gᵀd), ``FK`` (the eight
+    trial objectives F(2^-k·d)), ``k`` (the first step with F_k ≤ F0 + 0.01·2^-k·delta, the
+    solvers' Armijo rule; None when no step passes) and ``margin`` (the smallest
+    |F_k − (F0 + 0.01·2^-k·delta)| over the steps tested up to and including k: how far the choice
+    is from flipping)."""
+    np = _np()
+    L = np.longdouble
+    Xa, s, y = _ld(Xa), _ld(s), _ld(ypm)
+    pen = np.asarray(penal).astype(bool)
+    g = -L(C) / 2 * ((s * y) @ Xa)
+    A = L(C) / 4 * ((Xa * s[:, None]).T @ Xa) + np.diag(pen.astype(L))
+    d = -_ld_solve(A, g)
+    zero = np.zeros_like(d)
+    F0 = logreg_objective(Xa, s, y, zero, C, False, pen)
+    delta = g @ d
+    FK = np.array([logreg_objective(Xa, s, y, d * L(2.0) ** -k, C, False, pen) for k in range(8)], dtype=L)
+    thr = F0 + L(0.01) * L(2.0) ** -np.arange(8) * delta
+    ok = FK <= thr
+    k = int(np.argmax(ok)) if ok.any() else None
+    margin = np.abs(FK - thr)[: (k + 1) if k is not None else 8].min()
+    return {"d": d, "A": A, "g": g, "F0": F0, "delta": delta, "FK": FK, "k": k, "margin": margin}
+
+
+def l1qp_kkt(H, g, w, penal, lam, d, tol=1e-12):
+    """Per-coordinate KKT residual of ``min_d gᵀd + ½dᵀHd + λ·Σ_{pen}|w_j + d_j|`` at ``d``: with
+    r = g + Hd and u = w + d, r_j + λ·sign(u_j) where penalised and u_j ≠ 0,
+    sign(r_j)·max(|r_j| − λ, 0) where penalised and u_j = 0, r_j where unpenalised.
+
+    Also the bound a cyclic coordinate descent stopped by "largest step of the last sweep ≤ tol"
+    must meet: coordinate j is exact when it is updated and every later step of that sweep moves
+    r_j by at most tol·|H_jk|, so |res_j| ≤ tol·Σ_k|H_jk| plus the f64 rounding of the terms of
+    r_j, 4·eps·(|g_j| + Σ_k|H_jk||d_k| + λ).  Returns ``(res, bound)``, longdouble [F1]."""
+    np = _np()
+    H, g, w, d = _ld(H), _ld(g), _ld(w), _ld(d)
+    pen = np.asarray(penal).astype(bool)
+    lam = np.longdouble(lam)
+    r, u = g + H @ d, w + d
+    at0 = np.sign(r) * np.maximum(np.abs(r) - lam, 0)
+    res = np.where(pen, np.where(u != 0, r + lam * np.sign(u), at0), r)
+    eps = np.longdouble(np.finfo(np.float64).eps)
+    aH = np.abs(H)
+    bound = np.longdouble(tol) * aH.sum(1) + 4 * eps * (np.abs(g) + aH @ np.abs(d) + lam)
+    return res, bound
+
+
+def lasso_gap_oracle(G, q, yy, n, alpha, w):
+    """sklearn's Gram-form duality gap (``enet_coordinate_descent_gram``, l2_reg = 0) of
+    ``½‖y − Xw‖² + α·n·‖w‖₁`` from G = XᵀX, q = Xᵀy, yy = yᵀy: with R² = yy − 2wᵀq + wᵀGw and
+    ν = max|q − Gw|, c = min(1, αn/ν), gap = ½R²(1 + c²) + αn‖w‖₁ − c·(yy − wᵀq)  (R² when c = 1).
+    Also the cancellation budget of an f64 evaluation of R² from its three terms,
+    ``8·eps·(yy + 2Σ|w_j q_j| + Σ|w_j||(Gw)_j|)``.  Returns ``(gap, budget)``."""
+    np = _np()
+    G, q, w = _ld(G), _ld(q), _ld(w)
+    yy, l1 = np.longdouble(yy), np.longdouble(alpha) * np.longdouble(n)
+    Gw = G @ w
+    wq = w @ q
+    R2 = yy - 2 * wq + w @ Gw
+    nu = np.abs(q - Gw).max()
+    if nu > l1:
+        c = l1 / nu
+        gp = (R2 + R2 * c * c) / 2
+    else:
+        c, gp = np.longdouble(1), R2
+    gap = gp + l1 * np.abs(w).sum() - c * (yy - wq)
+    eps = np.longdouble(np.finfo(np.float64).eps)
+    budget = 8 * eps * (np.abs(yy) + 2 * np.abs(w * q).sum() + (np.abs(w) * np.abs(Gw)).sum())
+    return gap, budget
+
+
+def moments_oracle(X, W, V=None):
+    """``G[p] = Σ_n W[p,n]·x_n x_nᵀ``, ``a[p] = Σ_n W[p,n]·x_n``, ``v[p] = Σ_n V[p,n]·x_n`` in
+    longdouble, and the magnitudes Σ|W x_i x_j|, Σ|W x_f|, Σ|V x_f| that scale the (n + 2)·eps bound of
+    an f64 sum of those terms in any order.  Returns ``(G, a, v, Gmag, amag, vmag)`` (v, vmag None
+    without V)."""
+    np = _np()
+    X, W = _ld(X), _ld(W)
+    aX, aW = np.abs(X), np.abs(W)
+    G = np.stack([(X * W[p][:, None]).T @ X for p in range(W.shape[0])])
+    Gmag = np.stack([(aX * aW[p][:, None]).T @ aX for p in range(W.shape[0])])
+    a, amag = W @ X, aW @ aX
+    if V is None:
+        return G, a, None, Gmag, amag, None
+    V = _ld(V)
+    return G, a, V @ X, Gmag, amag, np.abs(V) @ aX
