@@ -159,7 +159,7 @@ class _HostKernels:
                             continue
                         dlw, drw = cw.double(), rw.double()
                         diff = drw * cg.double() - dlw * rg.double()
-                        gain = torch.where(ok, diff / dlw * diff / drw, torch.full_like(dlw, -1.0))
+                        gain = torch.where(ok, (diff / dlw) * (diff / drw), torch.full_like(dlw, -1.0))
                         k = int(torch.argmax(gain))
                         gv = float(gain[k])
                         if gv > best[0]:

@@ -264,7 +264,7 @@ __device__ __forceinline__ void scan_feature(const long long* __restrict__ hf, i
     if ((double)lw < min_leaf_q || (double)rw < min_leaf_q) continue;
     const double dlw = (double)lw, drw = (double)rw;
     const double diff = drw * (double)lg - dlw * (double)rg;
-    const double gain = diff / dlw * diff / drw;
+    const double gain = (diff / dlw) * (diff / drw);  // symmetric in the two sides: a mirrored cut ties bit for bit
     if (gain > best_gain) { best_gain = gain; best_bin = bb; }
   }
   // wave argmax, lowest bin on ties
@@ -293,7 +293,7 @@ __device__ __forceinline__ void scan_feature_small(const long long* hf, int nb, 
     if ((double)lw < min_leaf_q || (double)rw < min_leaf_q) continue;
     const double dlw = (double)lw, drw = (double)rw;
     const double diff = drw * (double)lg - dlw * (double)rg;
-    const double gain = diff / dlw * diff / drw;
+    const double gain = (diff / dlw) * (diff / drw);  // symmetric in the two sides: a mirrored cut ties bit for bit
     if (gain > best_gain) { best_gain = gain; best_bin = j; }
   }
 }

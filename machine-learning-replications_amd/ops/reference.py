@@ -4,6 +4,11 @@ These define the semantics the gfx950 HIP kernels must reproduce and run the
 host (CPU) path.  They follow the algorithms the reference delegates to
 (libsvm / sklearn trees / liblinear), re-derived from the published math; see
 the per-function notes and SURVEY.md §2.2 (E2-E12).
+
+GBDT training oracles (Python ints, Fractions, longdouble; nothing shared with
+models/hist_gbdt.py): ``gbdt_q``, ``gbdt_hist_oracle``, ``gbdt_split_oracle`` (with
+``GbdtSplit.certify`` and ``gbdt_split_children``), ``gbdt_bag_oracle``,
+``gbdt_route_oracle``, ``gbdt_route_r2_oracle``, ``gbdt_apply_prep_oracle``.
 """
 from __future__ import annotations
 
@@ -1745,3 +1750,291 @@ def moments_oracle(X, W, V=None):
         return G, a, None, Gmag, amag, None
     V = _ld(V)
     return G, a, V @ X, Gmag, amag, np.abs(V) @ aX
+
+
+# ----------------------------------------------------------------------------- GBDT training oracles
+# Written from the header of ops/csrc/gbdt.hip (what each kernel is documented to compute), in Python
+# ``int``, ``fractions.Fraction`` and numpy longdouble.  Nothing here imports models/hist_gbdt.py, and
+# the bagging hash is the Python-int ``_splitmix64_py`` above, not a tensor transcription.
+GBDT_U = 2.0 ** -53             # f64 unit roundoff
+GBDT_LEAF_EPS = 2.220446049250313e-16
+# relative f64 error of the device's per-row deviance and w·r² expressions (exp, log1p, one division
+# and a few products).  No ulp table of the device math library ships with the toolchain, so this is
+# twice the largest per-row discrepancy measured on an MI355X against the longdouble oracle: one row per
+# model, 8192 rows, the deviance at scale 2^48 on rows with |x| ≥ 1 and w·r² at 2^50 on rows with x ≥ ¼.
+# No row was off by more than one fixed-point unit, which is 31.93u relative at the smallest such x —
+# the resolution of the measurement, so an upper bound.  tests/test_gbdt_reference_gpu.py
+# ::test_apply_prep_row_error_within_measured repeats the measurement and asserts it stays within
+# GBDT_EPS_MEASURED.  At the scales the fit uses (2^26, 2^40) the ε term adds < 2^-6 unit per row to the
+# 1 unit each row is granted, so the sums are in effect tested to ± one unit per row whatever ε is.
+GBDT_EPS_MEASURED = 32 * GBDT_U
+GBDT_EPS_F64 = 2 * GBDT_EPS_MEASURED
+
+
+def gbdt_q(v, shift: int) -> int:
+    """``rint_half_even(v · 2^shift)`` of a float taken exactly (``round`` of a Fraction is exact and
+    rounds halves to even)."""
+    from fractions import Fraction
+    return round(Fraction(float(v)) * (1 << shift))
+
+
+def gbdt_hist_oracle(bins, nbins, g, h, w, node, node0: int, NL: int, shift: int):
+    """int64 ``[B, NL, F, 256, 3]``: for every row of model b with ``w > 0`` whose node lies in
+    ``node0 .. node0+NL-1``, the exact fixed-point (g, h, w) added in Python ints to its bin of every
+    feature.  ``bins`` [F, n] uint8, ``g``/``h``/``w`` [B, n] float32, ``node`` [B, n]."""
+    np = _np()
+    bins, g, h, w, node = (np.asarray(a) for a in (bins, g, h, w, node))
+    B, n = g.shape
+    F = bins.shape[0]
+    H = [0] * (B * NL * F * 768)
+    for b in range(B):
+        for i in range(n):
+            nd = int(node[b, i]) - node0
+            if nd < 0 or nd >= NL or not w[b, i] > 0:
+                continue
+            q = (gbdt_q(g[b, i], shift), gbdt_q(h[b, i], shift), gbdt_q(w[b, i], shift))
+            for f in range(F):
+                k = (((b * NL + nd) * F + f) * 256 + int(bins[f, i])) * 3
+                H[k] += q[0]
+                H[k + 1] += q[1]
+                H[k + 2] += q[2]
+    assert max(abs(v) for v in H) < 1 << 63
+    return np.array(H, dtype=np.int64).reshape(B, NL, F, 256, 3)
+
+
+class GbdtSplit:
+    """One node's exact split analysis (``gbdt_split_oracle``).
+
+    ``kind``: 'empty' (Σw ≤ 0: the kernel writes feat = −3 and nothing else), 'leaf' or 'split'.
+    ``cands``: {(f, j): (gain, err)} — exact proxy gain as a Fraction and the relative f64 error bound
+    of the kernel's value of it.  ``best``: the exact maximiser after the tie rule.  ``decided``: no
+    candidate outside best's identical-integer class (or tied with it at a gain of exactly 0, which
+    the kernel computes exactly) comes within the two error bounds of it."""
+
+    def certify(self, f: int, j: int):
+        """None when the kernel's choice (f, j) is admissible, else the reason."""
+        if (f, j) not in self.cands:
+            return f"({f}, {j}) is not a candidate"
+        gk, ek = self.cands[(f, j)]
+        gb, eb = self.cands[self.best]
+        if gk < gb * (1 - ek - eb):
+            return f"gain({f}, {j}) = {float(gk):.17g} < best {self.best} {float(gb):.17g} beyond the f64 margin"
+        if self.decided and (f, j) != self.best:
+            return f"decided case: ({f}, {j}) chosen, exact best is {self.best}"
+        return None
+
+
+def gbdt_split_oracle(hist, nbins, lo_val, hi_val, r2: int, shift: int, min_leaf_q: int, min_split_q: int,
+                      rank=None) -> GbdtSplit:
+    """The split of one node from its integer histogram ``hist[f][bin] = (Σg, Σh, Σw)`` (fixed point,
+    scale 2^shift), per the rule in gbdt.hip's header: node totals are feature 0's sums; a cut after
+    bin j < nb−1 is a candidate when both sides carry ≥ ``min_leaf_q`` and the node ≥ ``min_split_q``;
+    the best cut maximises the friedman_mse proxy ``(rw·lg − lw·rg)² / (lw·rw)``, ties to the lowest
+    feature (lowest ``rank[f]`` when given), then the lowest bin; the node is a leaf without a candidate
+    or when its impurity ``r2/tw − (tg/tw)²`` ≤ 2^-52.
+
+    Error bound of the kernel's f64 gain ``(diff/dlw)·(diff/drw)`` (a product of two quotients, so the
+    same bits when a mirrored cut swaps the sides), first order in u = 2^-53.  Each
+    int64→f64 conversion is off by ≤ u, so a product of two converted integers is off by ≤ 3u of
+    itself and ``diff = fl(fl(drw·dlg) − fl(dlw·drg))`` by ≤ 3u·(|rw·lg| + |lw·rg|) + u·|diff|, i.e.
+    (3κ + 1)u relative with κ = (|rw·lg| + |lw·rg|) / |rw·lg − lw·rg|.  diff enters twice: 2(3κ + 1)u;
+    the divisors dlw, drw carry u each; two divisions and one product round once each: 3u.  Sum:
+    (6κ + 7)u.  A fused multiply-add removes a rounding and only lowers it.  With an exact diff = 0 and
+    all four integers below 2^53 both products are the same real number, so the kernel's gain is
+    exactly 0 (error 0); above 2^53 such a candidate is given an infinite bound."""
+    from fractions import Fraction
+    u = Fraction(1, 1 << 53)
+    F = len(nbins)
+    o = GbdtSplit()
+    o.hist, o.nbins, o.lo_val, o.hi_val = hist, nbins, lo_val, hi_val
+    nb0 = int(nbins[0])
+    o.tg, o.th, o.tw = (sum(int(hist[0][j][s]) for j in range(nb0)) for s in range(3))
+    o.cands, o.key, o.best, o.decided = {}, {}, None, True
+    if o.tw <= 0:
+        o.kind = "empty"
+        return o
+    o.imp = Fraction(int(r2), o.tw) - Fraction(o.tg, o.tw) ** 2
+    if o.tw >= min_split_q:
+        for f in range(F):
+            lw = lg = 0
+            for j in range(int(nbins[f]) - 1):
+                lg += int(hist[f][j][0])
+                lw += int(hist[f][j][2])
+                rw, rg = o.tw - lw, o.tg - lg
+                if lw < min_leaf_q or rw < min_leaf_q:
+                    continue
+                a, c = rw * lg, lw * rg
+                if a != c:
+                    err = (6 * Fraction(abs(a) + abs(c), abs(a - c)) + 7) * u
+                elif max(abs(lw), abs(rw), abs(lg), abs(rg)) < 1 << 53:
+                    err = Fraction(0)
+                else:
+                    err = Fraction(1 << 60)
+                o.cands[(f, j)] = (Fraction((a - c) ** 2, lw * rw), err)
+                o.key[(f, j)] = tuple(sorted([(lw, lg), (rw, rg)]))   # a mirrored cut swaps the sides
+    if not o.cands or o.imp <= Fraction(GBDT_LEAF_EPS):
+        o.kind = "leaf"
+        return o
+    o.kind = "split"
+    rk = (lambda f: f) if rank is None else (lambda f: int(rank[f]))
+    gmax = max(g for g, _ in o.cands.values())
+    top = [k for k, (g, _) in o.cands.items() if g == gmax]
+    o.best = min(top, key=lambda k: (rk(k[0]), k[1]))
+    gb, eb = o.cands[o.best]
+    for k, (g, e) in o.cands.items():
+        if o.key[k] == o.key[o.best] or (g == gb and e == 0 and eb == 0):
+            continue      # identical integers, or both gains an exact 0 in f64 too: the tie rule decides
+        if not g < gb * (1 - e - eb):
+            o.decided = False
+    return o
+
+
+def gbdt_split_children(o: GbdtSplit, f: int, j: int):
+    """For the cut (f, j) of ``o``: ``(left, right, thr)`` — the children's (Σw, Σg, Σh) as ints and the
+    f64 threshold: the midpoint ``a/2 + c/2`` of bin j's highest value ``a`` and the lowest value ``c`` of
+    the next non-empty bin (the search stops at the last bin, empty or not); ``a`` when the midpoint
+    equals ``c`` or overflows."""
+    hf = o.hist[f]
+    lg, lh, lw = (sum(int(hf[b][s]) for b in range(j + 1)) for s in range(3))
+    hi = j + 1
+    while hi < int(o.nbins[f]) - 1 and int(hf[hi][2]) == 0:
+        hi += 1
+    a, c = float(o.hi_val[f][j]), float(o.lo_val[f][hi])
+    t = a / 2.0 + c / 2.0
+    if t == c or math.isinf(t):
+        t = a
+    return (lw, lg, lh), (o.tw - lw, o.tg - lg, o.th - lh), t
+
+
+def gbdt_bag_oracle(seed: int, stage: int, gidx: int, subsample: float) -> bool:
+    """Row ``gidx`` (global index) is in stage ``stage``'s bag of the model with u64 ``seed`` iff the top
+    24 bits of splitmix64(seed ⊕ splitmix64(stage·2^40 ⊕ gidx)) are below round(subsample·2^24)."""
+    M = (1 << 64) - 1
+    k = _splitmix64_py(((int(stage) << 40) ^ int(gidx)) & M)
+    return (_splitmix64_py((int(seed) & M) ^ k) >> 40) < int(round(subsample * 16777216.0))
+
+
+def gbdt_route_oracle(bins, node, feat, blo, node0: int, NL: int):
+    """Rows whose node lies in ``node0 .. node0+NL-1`` and has ``feat ≥ 0`` move to child
+    ``2·node + 1`` (``bins[feat] ≤ blo``) or ``2·node + 2``; every other row stays.  Returns the new
+    [B, n] int64 nodes and the bool mask of moved rows."""
+    np = _np()
+    bins, node, feat, blo = (np.asarray(a) for a in (bins, node, feat, blo))
+    B, n = node.shape
+    new = node.astype(np.int64).copy()
+    moved = np.zeros((B, n), dtype=bool)
+    for b in range(B):
+        for i in range(n):
+            nd = int(node[b, i])
+            if nd < node0 or nd >= node0 + NL or int(feat[b, nd]) < 0:
+                continue
+            new[b, i] = 2 * nd + (1 if int(bins[int(feat[b, nd]), i]) <= int(blo[b, nd]) else 2)
+            moved[b, i] = True
+    return new, moved
+
+
+def gbdt_route_r2_oracle(g, w, new, moved, NN: int, shift: int):
+    """[B, NN] Python-int child sums of ``rint(w·(g/w)²·2^shift)`` over the moved rows with w > 0 (exact
+    for w ∈ {0, 1}, where r = g and g² is exact in f64)."""
+    from fractions import Fraction
+    np = _np()
+    g, w = np.asarray(g), np.asarray(w)
+    B, n = g.shape
+    out = [[0] * NN for _ in range(B)]
+    for b in range(B):
+        for i in np.nonzero(moved[b] & (w[b] > 0))[0]:
+            wi, gi = Fraction(float(w[b, i])), Fraction(float(g[b, i]))
+            out[b][int(new[b, i])] += round(gi * gi / wi * (1 << shift))
+    return out
+
+
+def _f32_round_info(v):
+    """float32 nearest to the longdouble ``v`` and its distance to the nearest f32 rounding boundary."""
+    np = _np()
+    f = v.astype(np.float32)
+    up = np.nextafter(f, np.float32(np.inf)).astype(np.longdouble)
+    dn = np.nextafter(f, np.float32(-np.inf)).astype(np.longdouble)
+    fl = f.astype(np.longdouble)
+    dist = np.minimum(np.abs(v - (fl + up) / 2), np.abs(v - (fl + dn) / 2))
+    return f, dist, np.maximum(up - fl, fl - dn)
+
+
+class GbdtPrep:
+    """Outputs of ``gbdt_apply_prep_oracle`` (arrays [B, n] unless noted)."""
+
+
+def gbdt_apply_prep_oracle(bins, y, w, raw, node, prev, lr: float, shift: int, dshift: int = 26,
+                           subsample: float = 1.0, seeds=None, row_off: int = 0, stage: int = 0) -> GbdtPrep:
+    """``gbdt_apply_prep`` in longdouble.  ``prev`` = (feat, blo, value) [B, NN] of the previous tree or
+    None at stage 0.  With a previous tree: the pending last-level split routes each row, ``raw`` gains
+    lr·value[leaf]; rows of the previous stage's bag add ``w·(y − σ(raw_before))²`` to their leaf's
+    ``prev_r2`` and the binomial deviance ``−2w(y·raw − log(1 + e^raw))`` of the updated raw to ``dev``.
+    Then g = w_t(y − p), h = w_t·p(1 − p) (float32) with this stage's in-bag weight w_t, and
+    ``cur_r2`` = Σ w_t(y − p)².
+
+    ``g_und`` / ``h_und`` mark rows whose longdouble value lies within 2^-50 relative of an f32 rounding
+    boundary: there either neighbour is right.  One departure from a pure relative band: the f64
+    expression ``y − p`` (and ``1 − p``) inherits the ABSOLUTE error of p, δp = 4u·p (exp, add, divide)
+    + 2u·|raw|·p(1 − p) (the rounding of raw + lr·value carried through σ), which no f64 kernel can
+    undercut.  Only on rows where δp exceeds the relative band — p next to 1 with y = 1, |raw| large —
+    does δp replace it (and is added to the one-f32-ulp tolerance); every other row keeps 2^-50 and one
+    ulp.  The fixed-point sums come as exact ints of the rounded longdouble terms with the budget
+    Σ_rows (1 + ε·|x|·scale), ε = ``GBDT_EPS_F64``; at the scales in use the ε term is below 2^-6 per row,
+    so the sums are in effect held to one unit per contributing row."""
+    np = _np()
+    ld = np.longdouble
+    bins, y, w, node = np.asarray(bins), np.asarray(y), np.asarray(w), np.asarray(node)
+    rawl = np.asarray(raw, dtype=np.float64).astype(ld)
+    B, n = w.shape
+    o = GbdtPrep()
+    wl = w.astype(ld)
+    wt, wp = wl.copy(), wl.copy()
+    if subsample < 1.0:
+        for b in range(B):
+            for i in range(n):
+                if not gbdt_bag_oracle(int(seeds[b]), stage, row_off + i, subsample):
+                    wt[b, i] = 0
+                if prev is None or not gbdt_bag_oracle(int(seeds[b]), stage - 1, row_off + i, subsample):
+                    wp[b, i] = 0
+    o.wt = wt.astype(np.float32)
+    yl = y.astype(ld)[None, :]
+    qs, ds = ld(2) ** shift, ld(2) ** dshift
+    eps = ld(GBDT_EPS_F64)
+
+    def fixed(x, scale, on):
+        q = np.where(on, np.rint(x * scale), 0)
+        bud = np.where(on, 1 + eps * np.abs(x) * scale, 0)
+        return q.astype(np.int64), bud
+
+    o.leaf = node.astype(np.int64)
+    if prev is not None:
+        feat, blo, value = (np.asarray(a) for a in prev)
+        NN = feat.shape[1]
+        o.leaf, _ = gbdt_route_oracle(bins, node, feat, blo, 0, NN)
+        r0 = yl - _lm_sigmoid(rawl)
+        q, bud = fixed(wp * r0 * r0, qs, wp > 0)
+        o.prev_r2 = [[int(q[b][o.leaf[b] == k].sum()) for k in range(NN)] for b in range(B)]
+        o.prev_r2_budget = [[float(bud[b][o.leaf[b] == k].sum()) for k in range(NN)] for b in range(B)]
+        o.step = ld(lr) * np.take_along_axis(np.asarray(value, dtype=np.float64), o.leaf, 1).astype(ld)
+        rawl = rawl + o.step
+        q, bud = fixed(wp * -2 * (yl * rawl - _lm_softplus(rawl)), ds, wp > 0)
+        o.dev = [int(q[b].sum()) for b in range(B)]
+        o.dev_budget = [float(bud[b].sum()) for b in range(B)]
+    o.raw = rawl
+    p = _lm_sigmoid(rawl)
+    r = yl - p
+    # 1 − p without cancellation: σ(−raw)
+    o.g, o.h = wt * r, wt * p * _lm_sigmoid(-rawl)
+    u = ld(GBDT_U)
+    dp = 4 * u * p + (2 * u * np.abs(rawl) * p * _lm_sigmoid(-rawl) if prev is not None else 0)
+    for name, v in (("g", o.g), ("h", o.h)):
+        f, dist, ulp = _f32_round_info(v)
+        band = ld(2.0 ** -50) * np.abs(v)
+        extra = np.where(dp > band, dp, 0)               # the saturated / cancelling rows only
+        setattr(o, name + "32", f)
+        setattr(o, name + "_und", (v != 0) & (dist <= np.maximum(band, extra)))   # w = 0: exactly 0
+        setattr(o, name + "_tol", ulp + extra)
+    q, bud = fixed(wt * r * r, qs, wt > 0)
+    o.cur_r2 = [int(q[b].sum()) for b in range(B)]
+    o.cur_r2_budget = [float(bud[b].sum()) for b in range(B)]
+    return o
