@@ -58,6 +58,18 @@ def tree_raw(x, feature, threshold, left, right, value, init: float, lr: float, 
     return ref.tree_raw(x, feature, threshold, left, right, value, init, lr)
 
 
+def _stack_model_args(pk):
+    """The model arguments every fused stack op of the extension takes after its inputs, from a
+    :class:`PackedStack`: F, the padded SV count, the tree table shape, −γ·log2(e) and the other
+    scalars, then the device pointers (stump table: zeros when the stack keeps its generic trees)."""
+    f, s, st = pk.forest, pk.sv, pk.stumps
+    stumps = (st.off.data_ptr(), st.pairs.data_ptr(), st.base) if st is not None else (0, 0, 0.0)
+    return (pk.F, s.mp, f.n_trees, f.max_nodes, -pk.gamma * 1.4426950408889634, pk.svc_b, pk.probA, pk.probB,
+            pk.gb_init, pk.gb_lr, pk.lr_b, pk.meta_w[0], pk.meta_w[1], pk.meta_w[2], pk.meta_b,
+            pk.mean.data_ptr(), pk.inv_scale.data_ptr(), s.svt.data_ptr(), s.sn.data_ptr(), s.coef.data_ptr(),
+            f.nodes.data_ptr(), f.values.data_ptr(), pk.lr_w.data_ptr(), *stumps)
+
+
 def stack_infer(x, pk, out=None, grid: int = 0, stream=None):
     """Fused P(class 1) of the whole HF stack (one kernel, one pass over ``x``).
     ``x``: [n, F] f32 or f64; ``pk``: :class:`PackedStack` on ``x``'s device.  Returns f32 on
@@ -74,15 +86,7 @@ def stack_infer(x, pk, out=None, grid: int = 0, stream=None):
             out = torch.empty(n, dtype=torch.float32, device=x.device)
         elif out.dtype != torch.float32 or out.numel() < n or not out.is_contiguous():
             raise ValueError("stack_infer: out must be a contiguous f32 buffer of >= n elements")
-        f, s, st = pk.forest, pk.sv, pk.stumps
-        ext().stack_infer(x.data_ptr(), int(x.dtype == torch.float64), n, F, s.mp, f.n_trees, f.max_nodes,
-                          -pk.gamma * 1.4426950408889634, pk.svc_b, pk.probA, pk.probB, pk.gb_init,
-                          pk.gb_lr, pk.lr_b, pk.meta_w[0], pk.meta_w[1], pk.meta_w[2], pk.meta_b,
-                          pk.mean.data_ptr(), pk.inv_scale.data_ptr(), s.svt.data_ptr(), s.sn.data_ptr(),
-                          s.coef.data_ptr(), f.nodes.data_ptr(), f.values.data_ptr(), pk.lr_w.data_ptr(),
-                          st.off.data_ptr() if st is not None else 0,
-                          st.pairs.data_ptr() if st is not None else 0,
-                          st.base if st is not None else 0.0,
+        ext().stack_infer(x.data_ptr(), int(x.dtype == torch.float64), n, *_stack_model_args(pk),
                           out.data_ptr(), int(grid),
                           stream if stream is not None else stream_ptr(x.device))
         return out[:n]
@@ -141,21 +145,13 @@ def _stack_shapley_device(x, background, pk, return_values: bool, grid: int):
     per = max(1, SHAPLEY_WS_BYTES // (8 * nS))
     v_all = torch.empty(n, nS, dtype=torch.float64, device=dev) if return_values else None
     ws = None if return_values else torch.empty(min(n, per), nS, dtype=torch.float64, device=dev)
-    f, s, st = pk.forest, pk.sv, pk.stumps
+    model = _stack_model_args(pk)
     sp = stream_ptr(dev)
     for p0 in range(0, n, per):
         p1 = min(n, p0 + per)
         v = v_all[p0:p1] if return_values else ws[:p1 - p0]
-        ext().stack_coalition(x32[p0:p1].data_ptr(), p1 - p0, bg32.data_ptr(), B, F, s.mp, f.n_trees,
-                              f.max_nodes, -pk.gamma * 1.4426950408889634, pk.svc_b, pk.probA, pk.probB,
-                              pk.gb_init, pk.gb_lr, pk.lr_b, pk.meta_w[0], pk.meta_w[1], pk.meta_w[2],
-                              pk.meta_b, pk.mean.data_ptr(), pk.inv_scale.data_ptr(), s.svt.data_ptr(),
-                              s.sn.data_ptr(), s.coef.data_ptr(), f.nodes.data_ptr(), f.values.data_ptr(),
-                              pk.lr_w.data_ptr(),
-                              st.off.data_ptr() if st is not None else 0,
-                              st.pairs.data_ptr() if st is not None else 0,
-                              st.base if st is not None else 0.0,
-                              v.data_ptr(), int(grid), sp)
+        ext().stack_coalition(x32[p0:p1].data_ptr(), p1 - p0, bg32.data_ptr(), B, *model, v.data_ptr(),
+                              int(grid), sp)
         ext().shapley_reduce(v.data_ptr(), p1 - p0, F, w.data_ptr(), phi[p0:p1].data_ptr(), sp)
         pred[p0:p1] = v[:, nS - 1]
         if p0 == 0:
@@ -219,15 +215,7 @@ def _stack_partial_device(x, pk, feat, value, return_ice: bool, grid: int):
     v32 = _c(value, torch.float32)
     pd = torch.empty(C, dtype=torch.float64, device=dev)
     ice = torch.empty(n, C, dtype=torch.float32, device=dev) if return_ice else None
-    f, s, st = pk.forest, pk.sv, pk.stumps
-    ext().stack_partial(x32.data_ptr(), n, k32.data_ptr(), v32.data_ptr(), C, F, s.mp, f.n_trees, f.max_nodes,
-                        -pk.gamma * 1.4426950408889634, pk.svc_b, pk.probA, pk.probB, pk.gb_init, pk.gb_lr,
-                        pk.lr_b, pk.meta_w[0], pk.meta_w[1], pk.meta_w[2], pk.meta_b, pk.mean.data_ptr(),
-                        pk.inv_scale.data_ptr(), s.svt.data_ptr(), s.sn.data_ptr(), s.coef.data_ptr(),
-                        f.nodes.data_ptr(), f.values.data_ptr(), pk.lr_w.data_ptr(),
-                        st.off.data_ptr() if st is not None else 0,
-                        st.pairs.data_ptr() if st is not None else 0,
-                        st.base if st is not None else 0.0,
+    ext().stack_partial(x32.data_ptr(), n, k32.data_ptr(), v32.data_ptr(), C, *_stack_model_args(pk),
                         pd.data_ptr(), ice.data_ptr() if ice is not None else 0, int(grid), stream_ptr(dev))
     return (pd, ice) if return_ice else pd
 

@@ -137,6 +137,35 @@ __device__ __forceinline__ float fast_exp(float x) {  // e^x via v_exp_f32 (2^x)
   return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
 }
 
+// libsvm's P(class 1) of a binary SVC from its decision value: Platt sigmoid (A, B), then the
+// iterative 2-class pairwise coupling, in f64 (svc_proba1, svc_oof and the fused stack kernels)
+__device__ __forceinline__ double couple_p1(double dec, double A, double B) {
+  const double fApB = dec * A + B;
+  double r01 = fApB >= 0 ? exp(-fApB) / (1.0 + exp(-fApB)) : 1.0 / (1.0 + exp(fApB));
+  r01 = fmin(fmax(r01, 1e-7), 1 - 1e-7);
+  const double r10 = 1.0 - r01;
+  const double q00 = r10 * r10, q11 = r01 * r01, q01 = -r10 * r01;
+  double p0 = 0.5, p1 = 0.5;
+  for (int it = 0; it < 100; ++it) {
+    double qp0 = q00 * p0 + q01 * p1;
+    double qp1 = q01 * p0 + q11 * p1;
+    double pqp = p0 * qp0 + p1 * qp1;
+    if (fmax(fabs(qp0 - pqp), fabs(qp1 - pqp)) < 0.0025) break;
+    double d = (-qp0 + pqp) / q00;
+    p0 += d;
+    pqp = (pqp + d * (d * q00 + 2 * qp0)) / (1 + d) / (1 + d);
+    qp0 = (qp0 + d * q00) / (1 + d);
+    qp1 = (qp1 + d * q01) / (1 + d);
+    p0 /= (1 + d);
+    p1 /= (1 + d);
+    d = (-qp1 + pqp) / q11;
+    p1 += d;
+    p0 /= (1 + d);
+    p1 /= (1 + d);
+  }
+  return p1;
+}
+
 // XCD-aware bijective block remap (8 XCDs; blocks b and b+8 share an XCD under
 // round-robin dispatch).  Speed only, never correctness.
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {

@@ -131,39 +131,11 @@ void rbf_decision(uintptr_t Z, int n, int F, uintptr_t SVt, uintptr_t sn, uintpt
 }
 
 // ------------------------------------------------------------------------------------------
-// Platt + coupling
-__device__ __forceinline__ double platt_couple_p1(double dec, double A, double B) {
-  const double fApB = dec * A + B;
-  double r01 = fApB >= 0 ? exp(-fApB) / (1.0 + exp(-fApB)) : 1.0 / (1.0 + exp(fApB));
-  r01 = fmin(fmax(r01, 1e-7), 1 - 1e-7);
-  const double r10 = 1.0 - r01;
-  const double q00 = r10 * r10, q11 = r01 * r01, q01 = -r10 * r01;
-  double p0 = 0.5, p1 = 0.5;
-  for (int it = 0; it < 100; ++it) {
-    double qp0 = q00 * p0 + q01 * p1;
-    double qp1 = q01 * p0 + q11 * p1;
-    double pqp = p0 * qp0 + p1 * qp1;
-    double err = fmax(fabs(qp0 - pqp), fabs(qp1 - pqp));
-    if (err < 0.0025) break;
-    double d = (-qp0 + pqp) / q00;
-    p0 += d;
-    pqp = (pqp + d * (d * q00 + 2 * qp0)) / (1 + d) / (1 + d);
-    qp0 = (qp0 + d * q00) / (1 + d);
-    qp1 = (qp1 + d * q01) / (1 + d);
-    p0 /= (1 + d);
-    p1 /= (1 + d);
-    d = (-qp1 + pqp) / q11;
-    p1 += d;
-    p0 /= (1 + d);
-    p1 /= (1 + d);
-  }
-  return p1;
-}
-
+// Platt + coupling (couple_p1, common.h)
 __global__ void svc_proba1_kernel(const float* __restrict__ dec, float* __restrict__ out, int n,
                                   double A, double B) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    out[i] = (float)platt_couple_p1((double)dec[i], A, B);
+    out[i] = (float)couple_p1((double)dec[i], A, B);
 }
 
 void svc_proba1(uintptr_t dec, uintptr_t out, int n, double A, double B, uintptr_t stream) {
@@ -187,7 +159,7 @@ __global__ void svc_oof_kernel(const double* __restrict__ dec, const int* __rest
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const int k = model[i];
     const float d = (float)(dec[i] - rho[k]);
-    meta[rows[i] * ld + col] = (double)(float)platt_couple_p1((double)d, AB[2 * k], AB[2 * k + 1]);
+    meta[rows[i] * ld + col] = (double)(float)couple_p1((double)d, AB[2 * k], AB[2 * k + 1]);
   }
 }
 
