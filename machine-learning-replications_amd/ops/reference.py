@@ -2038,3 +2038,406 @@ def gbdt_apply_prep_oracle(bins, y, w, raw, node, prev, lr: float, shift: int, d
     o.cur_r2 = [int(q[b].sum()) for b in range(B)]
     o.cur_r2_budget = [float(bud[b].sum()) for b in range(B)]
     return o
+
+
+# ----------------------------------------------------------------------------- exact-SMO SVC oracles
+# numpy and Python only, written from Fan, Chen and Lin (2005), libsvm's published Solver rules
+# (select_working_set, the pair update, calculate_rho), Lin, Lin and Weng (2007) for the sigmoid fit
+# and sklearn's documented gamma='scale'.  Like the working-set section above, nothing here imports
+# torch or models/smo.py: the kernels of ops/csrc/svm.hip, svm_coop.hip and stackdev.hip's svm_gamma
+# and the host mirrors in models/smo.py are all on the other side of every comparison.
+SMO_U = 2.0 ** -53              # f64 unit roundoff
+SMO_TAU = 1e-12                 # libsvm's TAU
+SMO_VARIANTS = ("ties_first", "no_tau", "clip_swapped", "rho_ub", "stop_after_select")
+
+
+def gram_kernel_error(Z32, ngl2e_f32):
+    """``(K, dK)`` [l, l], longdouble: the RBF Gram ``K_ab = 2^(ngl2e·‖z_a − z_b‖²)`` of the f32 rows
+    ``Z32`` with the scale read back from the stored f32 (it IS the scale, as in
+    :func:`ws_kernel_error`), distances by direct differences in longdouble, and the forward bound
+    of ``gram_rbf_kernel``'s f32 evaluation
+
+        na = fma-chain ‖a‖², nb likewise;  dot = MFMA(a, b);
+        d2 = max(fma(−2, dot, fl(na + nb)), 0);  K̂ = exp2(fl(ngl2e·d2)),  K̂_aa = 1.
+
+    Term by term, with U = 2⁻²⁴, γ_n = nU/(1 − nU), mag = ‖a‖² + ‖b‖² + 2|a|·|b| (|a|·|b| the dot
+    product of the absolute values) and g2 = −ngl2e:
+
+    * the two norm chains: fma(z, z, s) over the padded width rounds once per step and the padding
+      adds exact zeros, so each is off by ≤ γ_F·‖x‖²;
+    * fl(na + nb): one rounding of a sum of two computed norms, ≤ U·(1 + γ_F)·(‖a‖² + ‖b‖²);
+    * the dot product through v_mfma_f32_32x32x2_f32: two roundings per term (its product and its
+      accumulation), in whatever order the unit takes them: ≤ γ_2F·|a|·|b|, doubled by the −2;
+    * the final fma rounds once: ≤ U·|d̂2| ≤ U·(1 + γ_2F)·mag;
+    * where nothing can round, nothing is budgeted: when the entries of both rows are integer
+      multiples of a power of two q and mag < 2²⁴·q², every product and every partial sum, in any
+      order, is a multiple of q² below 2²⁴·q², hence an f32: Δd2 = 0 for that pair (this is what
+      lets the tests tell a scale that is off by one ulp from the kernel's);
+    * the clamp at 0 only moves d̂2 towards the true d2 ≥ 0;
+    * fl(ngl2e·d̂2): ≤ U·g2·(d2 + Δd2) in the exponent;
+    * exp2 itself: K̂ = 2^(e + δ)·(1 + ε), |ε| ≤ EPS_EXP2, plus _TINY for a flushed result.
+
+    So Δd2 = (γ_F + U(1 + γ_F))(‖a‖² + ‖b‖²) + 2γ_2F|a|·|b| + U(1 + γ_2F)·mag, the exponent is off by
+    δ ≤ g2·Δd2 + U·g2·(d2 + Δd2), and dK = K·((2^δ − 1)(1 + EPS_EXP2) + EPS_EXP2) + _TINY.  With
+    row norms near 1e3 and ‖a − b‖ = O(1), Δd2 is O(1) (cancellation), and dK legitimately reaches
+    O(K).  The diagonal is forced: K_aa = 1, dK_aa = 0."""
+    np = _np()
+    L = np.longdouble
+    Z = np.asarray(Z32, dtype=np.float32).astype(L)
+    l, F = Z.shape
+    e2 = L(np.float32(ngl2e_f32))
+    g2 = -e2
+    U = L(_U)
+    gF, g2F = F * U / (1 - F * U), 2 * F * U / (1 - 2 * F * U)
+    nrm = (Z * Z).sum(1)
+    aZ = np.abs(Z)
+    # the lowest set bit of each row's entries: the row's values are integer multiples of quant
+    mant, ex = np.frexp(np.asarray(Z32, dtype=np.float32).astype(np.float64))
+    mi = np.round(mant * 2.0 ** 24).astype(np.int64)
+    low = np.where(mi != 0, ex - 24 + np.log2((mi & -mi).astype(np.float64) + (mi == 0)), 0.0)
+    quant = np.exp2(np.where(mi != 0, low, np.inf).min(1, initial=126.0))
+    K = np.empty((l, l), dtype=L)
+    dK = np.empty((l, l), dtype=L)
+    step = max(1, (1 << 20) // max(1, l * F))
+    ln2 = np.log(L(2))
+    with np.errstate(under="ignore", over="ignore", invalid="ignore"):
+        for s in range(0, l, step):
+            diff = Z[s:s + step, None, :] - Z[None, :, :]
+            d2 = (diff * diff).sum(-1)
+            cross = aZ[s:s + step] @ aZ.T
+            nn = nrm[s:s + step, None] + nrm[None, :]
+            dd2 = (gF + U * (1 + gF)) * nn + 2 * g2F * cross + U * (1 + g2F) * (nn + 2 * cross)
+            qq = np.minimum(quant[s:s + step, None], quant[None, :]) ** 2
+            dd2 = np.where(nn + 2 * cross < qq * 2.0 ** 24, 0, dd2)
+            de = g2 * dd2 + U * g2 * (d2 + dd2)
+            k = np.exp2(e2 * d2)
+            x = np.expm1(ln2 * de)
+            K[s:s + step] = k
+            dK[s:s + step] = np.where(k > 0, k * (x * (1 + L(EPS_EXP2)) + L(EPS_EXP2)), 0) + L(_TINY)
+    ix = np.arange(l)
+    K[ix, ix] = 1
+    dK[ix, ix] = 0
+    return K, dK
+
+
+def gram_inside(Khat, K, dK):
+    """Entries of a computed Gram that :func:`gram_kernel_error` admits: within dK of K, and at most
+    1 (the clamp makes the exponent non-positive, and exp2 of a non-positive f32 never exceeds 1)."""
+    np = _np()
+    Kh = np.asarray(Khat).astype(np.longdouble)
+    return (np.abs(Kh - K) <= dK) & (Kh <= 1)
+
+
+class SmoResult:
+    """What :func:`smo_oracle` returns: ``alpha`` [l] f64, ``rho``, ``iters`` (pair updates made),
+    ``pairs`` (the (i, j) of every update, in order), ``gap`` (the last m − M the stop rule saw),
+    ``G`` (the incrementally updated gradient, f64) and ``drift`` [l] (forward bound of G − (Qα − 1))."""
+    __slots__ = ("alpha", "rho", "iters", "pairs", "gap", "G", "drift")
+
+    def __iter__(self):
+        return iter((self.alpha, self.rho, self.iters, self.pairs, self.drift))
+
+
+def smo_oracle(K, npos, Cp, Cn, eps, max_iter, variant=None):
+    """libsvm's Solver::Solve for C-SVC without shrinking, on the stored kernel matrix ``K``
+    (rounded to f32 here: libsvm keeps Q as float), the first ``npos`` points y = +1.
+
+    Plain float64, one IEEE operation at a time in libsvm's operation order (numpy's elementwise
+    multiply and add are separate roundings: no fused operation anywhere):
+
+    * start: α = 0, G = −1;
+    * first selection: i = argmax over I_up of −y_t G_t, ``>=`` so ties go to the LAST index;
+    * second selection over t ∈ I_low with b = Gmax + y_t G_t > 0: a = QD_i + QD_t − 2·K_it (QD the
+      diagonal; a ≤ 0 → τ = 1e-12), minimise −b²/a, ``<=`` so ties go to the LAST index.  Gmax2 =
+      max over I_low of y_t G_t is taken in the same sweep, over every member of I_low;
+    * stop rule: m − M = Gmax + Gmax2 < eps, or no candidate t.  It depends on the two maxima only,
+      not on the chosen t: it is tested before the second choice is used;
+    * the pair update with its four clipping cases (y_i ≠ y_j: δ = (−G_i − G_j)/a with a = QD_i +
+      QD_j + 2Q_ij; y_i = y_j: δ = (G_i − G_j)/a with a = QD_i + QD_j − 2Q_ij; a ≤ 0 → τ);
+    * G_t += Q_it·Δα_i + Q_jt·Δα_j with Q_it = y_i y_t K_it (a sign flip, exact);
+    * ``calculate_rho``: the index-ordered sum of y G over the free points divided by their count,
+      else (ub + lb)/2 (:func:`svc_kkt`'s sets).
+
+    ``drift``: G is updated incrementally, Qα − 1 (Q the stored f32 entries, α the returned one)
+    is what it stands for.  One update computes pa = fl(Q_it·Δα_i), pb = fl(Q_jt·Δα_j), s = fl(pa +
+    pb), G' = fl(G + s) with Δα = fl(α_new − α_old): five roundings, each ≤ 2⁻⁵³ times the computed
+    magnitude, so the update moves G_t away from the exact sum by at most
+    2⁻⁵³·(2|pa| + 2|pb| + |s| + |G'|)·(1 + 2⁻⁵⁰), and the drift is the sum of that over the replayed
+    updates (the exact increments telescope to the returned α).
+
+    ``variant``: one of ``SMO_VARIANTS``, a deliberately WRONG rule, for the tests that show the
+    comparison with libsvm notices each of them: first-index ties, no τ floor, a swapped clipping
+    case (the y_i ≠ y_j upper clip compares with C_j − C_i), ρ = ub with no free vector, and the
+    stop rule evaluated on the selected second index instead of on Gmax2."""
+    np = _np()
+    assert variant is None or variant in SMO_VARIANTS, variant
+    K32 = np.asarray(K, dtype=np.float32)
+    l = K32.shape[0]
+    pos, y, C = _ws_labels(l, npos, Cp, Cn)
+    QD = np.diagonal(K32).astype(np.float64)
+    G = -np.ones(l)
+    alpha = np.zeros(l)
+    drift = np.zeros(l)
+    pairs = []
+    gap = 0.0
+    last = variant != "ties_first"
+    floor = variant != "no_tau"
+    ninf = -np.inf
+
+    def pick(v, best):
+        w = np.flatnonzero(v == best)
+        return int(w[-1] if last else w[0])
+
+    it = 0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        while it < max_iter:
+            up = np.where(pos, alpha < C, alpha > 0)
+            if not up.any():
+                break
+            yG = np.where(pos, G, -G)
+            v = np.where(up, -yG, ninf)
+            Gmax = v.max()
+            i = pick(v, Gmax)
+            Ki = K32[i].astype(np.float64)
+            low = np.where(pos, alpha > 0, alpha < C)
+            Gmax2 = yG[low].max() if low.any() else ninf
+            b = Gmax + yG
+            cand = low & (b > 0)
+            a = (QD[i] + QD) - 2.0 * Ki
+            if floor:
+                a = np.where(a <= 0, SMO_TAU, a)
+            obj = np.where(cand, -(b * b) / a, np.inf)
+            j = pick(obj, obj[cand].min()) if cand.any() else -1
+            gap = Gmax + Gmax2
+            if variant == "stop_after_select":
+                if j < 0 or Gmax + yG[j] < eps:
+                    break
+            elif gap < eps or j < 0:
+                break
+            yi, yj = y[i], y[j]
+            Ci, Cj = C[i], C[j]
+            Qij = yi * yj * float(K32[i, j])
+            ai_old, aj_old = alpha[i], alpha[j]
+            ai, aj = ai_old, aj_old
+            if yi != yj:
+                a2 = (QD[i] + QD[j]) + 2.0 * Qij
+                if a2 <= 0 and floor:
+                    a2 = SMO_TAU
+                delta = (-G[i] - G[j]) / a2
+                diff = ai - aj
+                ai += delta
+                aj += delta
+                if diff > 0:
+                    if aj < 0:
+                        aj, ai = 0.0, diff
+                else:
+                    if ai < 0:
+                        ai, aj = 0.0, -diff
+                if diff > (Cj - Ci if variant == "clip_swapped" else Ci - Cj):
+                    if ai > Ci:
+                        ai, aj = Ci, Ci - diff
+                else:
+                    if aj > Cj:
+                        aj, ai = Cj, Cj + diff
+            else:
+                a2 = (QD[i] + QD[j]) - 2.0 * Qij
+                if a2 <= 0 and floor:
+                    a2 = SMO_TAU
+                delta = (G[i] - G[j]) / a2
+                sm = ai + aj
+                ai -= delta
+                aj += delta
+                if sm > Ci:
+                    if ai > Ci:
+                        ai, aj = Ci, sm - Ci
+                else:
+                    if aj < 0:
+                        aj, ai = 0.0, sm
+                if sm > Cj:
+                    if aj > Cj:
+                        aj, ai = Cj, sm - Cj
+                else:
+                    if ai < 0:
+                        ai, aj = 0.0, sm
+            dai, daj = ai - ai_old, aj - aj_old
+            pa = ((yi * y) * Ki) * dai
+            pb = ((yj * y) * K32[j].astype(np.float64)) * daj
+            s = pa + pb
+            G = G + s
+            drift += SMO_U * (1 + 2.0 ** -50) * (2 * np.abs(pa) + 2 * np.abs(pb) + np.abs(s) + np.abs(G))
+            alpha[i], alpha[j] = ai, aj
+            pairs.append((i, j))
+            it += 1
+            if not (np.isfinite(ai) and np.isfinite(aj)):      # only a wrong variant gets here
+                break
+    out = SmoResult()
+    kkt = svc_kkt(alpha, G, npos, Cp, Cn)
+    free = (alpha > 0) & (alpha < C)
+    yG = np.where(pos, G, -G)
+    if free.any():
+        rho = float(np.cumsum(yG[free])[-1] / int(free.sum()))      # libsvm's index-ordered sum
+    elif variant == "rho_ub":
+        ubm = np.where(pos, alpha <= 0, alpha >= C)
+        rho = float(yG[ubm].min()) if ubm.any() else np.inf
+    else:
+        rho = float(kkt["rho"])
+    out.alpha, out.rho, out.iters, out.pairs, out.gap, out.G, out.drift = alpha, rho, it, pairs, float(gap), G, drift
+    return out
+
+
+# f64 must also DETERMINE each Newton direction: the determinant h11·h22 − h21² of sums of n (or
+# ``depth``) terms is known to (n + 8)·2⁻⁵³·(h11·h22 + h21²) at best, so the direction carries that over
+# |det| as a relative error.  Runs where it exceeds 2⁻²⁰ are undecided: with a Hessian that is singular
+# up to the 1e-12 ridge (a constant decision value) the ratio is of order 1e-2, and f64 and longdouble
+# runs that take the same branches still end percent apart; on regular inputs it is below 1e-11.
+PLATT_DIRECTION_MAX = 2.0 ** -20
+
+
+class PlattResult:
+    """What :func:`platt_oracle` returns.  ``A, B``: the fit; ``iters``: Newton iterations made;
+    ``capped``: the run ended at the iteration cap or at the minimum step instead of the stop rule;
+    ``margin``: the smallest |f_trial − (f + 1e-4·step·∇·d)| over every backtracking test of the run
+    (inf when none was made); ``stop_margin``: the smallest | max|∇| − 1e-5 | over the stop tests;
+    ``direction``: the largest relative error f64 leaves in a Newton direction (see
+    ``PLATT_DIRECTION_MAX``); ``decided``: every such test lies further from its threshold than
+    the f64 evaluation error there (:meth:`evaluate`'s bounds) and every direction is determined,
+    so an f64 implementation takes the same branches through the same iterates."""
+
+    def __init__(self, dec, labels, T, depth=None):
+        np = _np()
+        self.T = T
+        self.depth = depth
+        self.d = np.asarray(dec, dtype=np.float64).astype(T)
+        lab = np.asarray(labels)
+        n1 = int((lab > 0).sum())
+        n0 = int(lab.size - n1)
+        self.n1, self.n0 = n1, n0
+        self.t = np.where(lab > 0, (T(n1) + 1) / (T(n1) + 2), 1 / (T(n0) + 2)).astype(T)
+
+    def evaluate(self, A, B):
+        """``(f, g1, g2, df, dg)`` at (A, B) in the oracle's float type: the objective
+        Σ t·z + log(1 + e^−z) (z = A·d + B, the overflow-free form of either sign), its gradient
+        (Σ d·(t − p), Σ (t − p)), and the bounds of an f64 evaluation of them in ANY summation order:
+        with u = 2⁻⁵³ and n points, a sum of n terms is off by ≤ γ_n·Σ|term| (γ_n = nu/(1 − nu); with
+        ``depth`` given, n is the depth of the summation tree instead — no term passes through more
+        additions than that: platt_kernel adds ≤ 16 values per thread, 6 wave levels and 16 wave
+        totals, platt_coop_kernel 8 workgroup totals more, numpy's pairwise sum fewer); each
+        term carries ≤ 8 further roundings (the product and sum of z, exp, log, the divisions: a
+        few ulp each, counted as 8u·|term|), and z's own error 2u(|A·d| + |B|) enters f through
+        |∂term/∂z| = |t − p| ≤ 1 and the gradient through p(1 − p) ≤ ¼:
+        df = u(n + 8)·Σ|term| + 2u·Σ(|A·d| + |B|) + u·N,  dg = u(n + 8)·Σ|d|·|t − p| + ½u·Σ|d|(|A·d| + |B|)
+        + 4u·Σ|d|·p (for g1; g2 is the same with |d| = 1, and dg is the larger of the two).  The last
+        term of each is absolute, one per point (N points): libsvm and the kernels evaluate
+        log(1 + e) and e/(1 + e), not log1p, and rounding 1 + e costs up to u absolutely in the log
+        whatever the size of the term (a well-classified negative's term is ≈ t₋·z, far below 1), and
+        a few u relative to p — not to t − p — in the gradient."""
+        np = _np()
+        T = self.T
+        A, B = T(A), T(B)
+        z = self.d * A + B
+        with np.errstate(over="ignore", under="ignore"):
+            e = np.exp(-np.abs(z))
+            lg = np.log1p(e)
+            terms = np.where(z >= 0, self.t * z, (self.t - 1) * z) + lg
+            p = np.where(z >= 0, e / (1 + e), 1 / (1 + e))
+        d1 = self.t - p
+        f, g1, g2 = terms.sum(), (self.d * d1).sum(), d1.sum()
+        n = self.d.size if self.depth is None else min(self.d.size, int(self.depth))
+        u = T(SMO_U)
+        zmag = np.abs(self.d * A) + abs(B)
+        absterm = np.abs(np.where(z >= 0, self.t * z, (self.t - 1) * z)) + lg
+        npts = self.d.size
+        df = u * (n + 8) * absterm.sum() + 2 * u * zmag.sum() + u * npts
+        ad = np.abs(self.d)
+        dg1 = u * (n + 8) * (ad * np.abs(d1)).sum() + u / 2 * (ad * zmag).sum() + 4 * u * (ad * p).sum()
+        dg2 = u * (n + 8) * np.abs(d1).sum() + u / 2 * zmag.sum() + 4 * u * p.sum()
+        return f, g1, g2, df, max(dg1, dg2)
+
+    def _hessian(self, A, B):
+        np = _np()
+        z = self.d * self.T(A) + self.T(B)
+        with np.errstate(over="ignore", under="ignore"):
+            e = np.exp(-np.abs(z))
+        pq = (e / (1 + e)) * (1 / (1 + e))
+        return (self.d * self.d * pq).sum(), pq.sum(), (self.d * pq).sum()
+
+
+def platt_oracle(dec, labels, dtype=None, depth=None):
+    """Platt's sigmoid fit by Lin, Lin and Weng's (2007) algorithm, as libsvm's ``sigmoid_train``
+    states it: targets t₊ = (N₊ + 1)/(N₊ + 2), t₋ = 1/(N₋ + 2); start A = 0, B = log((N₋ + 1)/(N₊ + 1));
+    Newton direction from the Hessian with a 1e-12 ridge on its diagonal; stop when both |∂/∂A| and
+    |∂/∂B| are below 1e-5; backtracking from step 1 by halving while step ≥ 1e-10, accepting when
+    f_trial < f + 1e-4·step·(∇·d); at most 100 iterations.  Everything in ``dtype`` (longdouble by
+    default; float64 runs the same code for the reference-against-reference margin of the tests;
+    ``depth``: see :meth:`PlattResult.evaluate`).
+    Returns a :class:`PlattResult` (``A``, ``B``, ``evaluate``, ``margin``, ``decided`` …)."""
+    np = _np()
+    T = np.longdouble if dtype is None else dtype
+    r = PlattResult(dec, labels, T, depth)
+    A, B = T(0), np.log((T(r.n0) + 1) / (T(r.n1) + 1))
+    f, g1, g2, df, dg = r.evaluate(A, B)
+    margin, stop_margin, decided = T(np.inf), T(np.inf), True
+    capped, it, direction = True, 0, T(0)
+    sigma, eps, min_step = T(1e-12), T(1e-5), T(1e-10)
+    for it in range(100):
+        for g in (g1, g2):
+            stop_margin = min(stop_margin, abs(abs(g) - eps))
+            decided = decided and abs(abs(g) - eps) > dg
+        if abs(g1) < eps and abs(g2) < eps:
+            capped = False
+            break
+        h11, h22, h21 = r._hessian(A, B)
+        h11, h22 = h11 + sigma, h22 + sigma
+        det = h11 * h22 - h21 * h21
+        nd = r.d.size if depth is None else min(r.d.size, int(depth))
+        direction = max(direction, (nd + 8) * T(SMO_U) * (h11 * h22 + h21 * h21) / abs(det))
+        dA = -(h22 * g1 - h21 * g2) / det
+        dB = -(-h21 * g1 + h11 * g2) / det
+        gd = g1 * dA + g2 * dB
+        step = T(1)
+        while step >= min_step:
+            nA, nB = A + step * dA, B + step * dB
+            nf, ng1, ng2, ndf, ndg = r.evaluate(nA, nB)
+            thr = f + T(0.0001) * step * gd
+            m = abs(nf - thr)
+            margin = min(margin, m)
+            decided = decided and m > ndf + df + 4 * T(SMO_U) * abs(thr)
+            if nf < thr:
+                A, B, f, g1, g2, df, dg = nA, nB, nf, ng1, ng2, ndf, ndg
+                break
+            step = step / 2
+        if step < min_step:
+            break
+    else:
+        it = 100
+    r.A, r.B, r.iters, r.capped = A, B, it, capped
+    r.margin, r.stop_margin, r.direction = margin, stop_margin, direction
+    r.decided = bool(decided and direction <= PLATT_DIRECTION_MAX)
+    return r
+
+
+def gamma_oracle(Z, offs, F):
+    """sklearn's ``gamma='scale'`` = 1/(F·Var(Z)) for every fit f over the rows offs[f] … offs[f+1] of
+    ``Z`` [rows, F], in longdouble: the population variance in two passes (the mean, then the mean
+    of the squared deviations), γ = 1 where the variance is exactly 0 (sklearn's rule), NaN where
+    a value is not finite.  Returns ``(gamma [K] longdouble, ngl2e [K] f32)`` with
+    ngl2e = f32(−γ·log2 e)."""
+    np = _np()
+    L = np.longdouble
+    Z = np.asarray(Z, dtype=np.float64).reshape(-1, F).astype(L)
+    offs = np.asarray(offs, dtype=np.int64)
+    g = np.empty(offs.size - 1, dtype=L)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for f in range(offs.size - 1):
+            z = Z[offs[f]:offs[f + 1]].ravel()
+            if z.size == 0:
+                g[f] = 1
+                continue
+            mean = z.sum() / z.size
+            d = z - mean
+            var = (d * d).sum() / z.size
+            g[f] = 1 / (F * var) if var != 0 else 1
+            if not np.isfinite(z).all():
+                g[f] = np.nan
+        ngl2e = (-g * np.log2(np.exp(L(1)))).astype(np.float32)
+    return g, ngl2e
