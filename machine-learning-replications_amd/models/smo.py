@@ -494,7 +494,7 @@ def _ws_ks(F: int) -> int:
     ks = (F + 1) // 2
     return 4 if ks <= 4 else 9 if ks <= 9 else 12 if ks <= 12 else 24
 
-# Device solver: "exact" = libsvm's pair sequence on a stored Gram (svm.hip / svm_coop.hip), "ws" =
+# Device solver: "exact" = libsvm's pair sequence on a stored Gram (svm.hip / svm_coop.hip on smo_steps.h), "ws" =
 # working-set decomposition (svm_ws.hip: q = 1024 slots solved inside one CU with the RBF recomputed
 # in registers, half of each working set reused, MFMA gradient updates; O(n) memory).  On the
 # bench's 10k problem the exact sequence is ~7.6k pairs at ~7.7 µs (cross-CU hand-offs), the

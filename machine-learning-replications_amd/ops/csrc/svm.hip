@@ -19,6 +19,7 @@
 // Licence: the pair rule, clipping, sigmoid_train and coupling follow LIBSVM (BSD-3-Clause, Chang & Lin;
 // notice in THIRD_PARTY_NOTICES.md at the repository root).
 #include "common.h"
+#include "smo_steps.h"
 
 namespace hfens {
 
@@ -125,55 +126,11 @@ struct SmoOut {
 
 constexpr int kSmoThreads = 1024;
 constexpr int kSmoWaves = kSmoThreads / 64;
-constexpr double kTau = 1e-12;
-constexpr double kInf = 1.0e300;
-
-// Block reduction of (a, b, idx): a → max; (b, idx) → arg-max with ties to the larger index.
-// Used with a = −∞ when only the arg-max is wanted.  All threads receive the result.
-struct Red3 {
-  double a, b;
-  int idx;
-};
-
-__device__ __forceinline__ void red3_combine(Red3& x, double a, double b, int idx) {
-  x.a = fmax(x.a, a);
-  if (b > x.b || (b == x.b && idx > x.idx)) { x.b = b; x.idx = idx; }
-}
-
-// Per-wave partial of a Red3 reduction: order-preserving u64 keys (exact for f64).
-struct Red3Part {
-  unsigned long long ka, kb;
-  int idx, pad;
-};
-
-// Block reduction: wave stage on DPP/permlane (u32 max of the key halves, then of the index among
-// the lanes holding the arg-max — no LDS round trips), one barrier, then every thread folds the
-// kSmoWaves partials.  Callers alternate two partial buffers so consecutive reductions need no
-// second barrier.
-__device__ __forceinline__ Red3 block_red3(Red3 v, Red3Part* sh) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long ka = f64_okey(v.a), kb = f64_okey(v.b);
-  const unsigned ah = wave_max_u32((unsigned)(ka >> 32));
-  const unsigned al = wave_max_u32((unsigned)(ka >> 32) == ah ? (unsigned)ka : 0u);
-  const unsigned bh = wave_max_u32((unsigned)(kb >> 32));
-  const unsigned bl = wave_max_u32((unsigned)(kb >> 32) == bh ? (unsigned)kb : 0u);
-  const bool top = (unsigned)(kb >> 32) == bh && (unsigned)kb == bl;
-  const unsigned bi = wave_max_u32(top ? (unsigned)(v.idx + 1) : 0u);
-  if (lane == 0) sh[wave] = Red3Part{((unsigned long long)ah << 32) | al, ((unsigned long long)bh << 32) | bl,
-                                     (int)bi - 1, 0};
-  __syncthreads();
-  Red3Part r = sh[0];
-#pragma unroll
-  for (int w = 1; w < kSmoWaves; ++w) {
-    const Red3Part p = sh[w];
-    r.ka = p.ka > r.ka ? p.ka : r.ka;
-    if (p.kb > r.kb || (p.kb == r.kb && p.idx > r.idx)) { r.kb = p.kb; r.idx = p.idx; }
-  }
-  return Red3{f64_from_okey(r.ka), f64_from_okey(r.kb), r.idx};
-}
 
 // Element ownership: thread `tid`, group g < K4, lane-of-vector e < 4 owns index
 // t = 4·(tid + g·kSmoThreads) + e, so every Gram-row read is one float4 per (thread, group).
+// The steps themselves (candidate rank, pair update, bound masks, ρ, block reduction) are
+// smo_steps.h's, shared with the cooperative kernels.
 template <int K4>
 __global__ __launch_bounds__(kSmoThreads) void smo_kernel(const SmoProb* __restrict__ probs,
                                                           const float* __restrict__ K,
@@ -189,16 +146,13 @@ __global__ __launch_bounds__(kSmoThreads) void smo_kernel(const SmoProb* __restr
   const float* Kp = K + P.koff;
   double* alpha = alpha_all + P.aoff;
   const int tid = threadIdx.x;
-  __shared__ Red3Part shA[kSmoWaves], shB[kSmoWaves];   // r1 / r2 partials (alternating)
+  __shared__ SmoRedPart shA[kSmoWaves], shB[kSmoWaves];   // r1 / r2 partials (alternating)
   __shared__ double pub[4];
+  __shared__ double ssum[2][kSmoWaves];
 
   double G[KM];
   float Qi[KM];
-  unsigned long long ypos = 0ull;   // y_t = +1
-  unsigned long long upm = 0ull;    // t ∈ I_up   (y=+1: α<C ; y=−1: α>0)
-  unsigned long long lowm = 0ull;   // t ∈ I_low  (y=+1: α>0 ; y=−1: α<C)
-  unsigned long long freem = 0ull;  // 0 < α < C
-  unsigned long long upperm = 0ull; // α = C
+  SmoMasks M;
 #pragma unroll
   for (int g = 0; g < K4; ++g)
 #pragma unroll
@@ -209,20 +163,19 @@ __global__ __launch_bounds__(kSmoThreads) void smo_kernel(const SmoProb* __restr
       Qi[k] = 0.f;
       if (t < P.l) {
         alpha[t] = 0.0;
-        const bool pos = t < P.npos;
-        if (pos) { ypos |= 1ull << k; upm |= 1ull << k; }   // α = 0 is at the lower bound
-        else lowm |= 1ull << k;
+        smo_masks_init(M, 1ull << k, t < P.npos);
       }
     }
   // ---- WSS step 1 for the first iteration
-  Red3 r1{-kInf, -kInf, -1};
+  double bb = -kSmoInf;
+  int bi = -1;
 #pragma unroll
   for (int k = 0; k < KM; ++k)
-    if ((upm >> k) & 1ull) {
+    if ((M.upm >> k) & 1ull) {
       const int t = 4 * (tid + (k >> 2) * kSmoThreads) + (k & 3);
-      red3_combine(r1, -kInf, ((ypos >> k) & 1ull) ? -G[k] : G[k], t);
+      smo_arg_take(bb, bi, ((M.ypos >> k) & 1ull) ? -G[k] : G[k], t);
     }
-  r1 = block_red3(r1, shA);
+  SmoRedPart r1 = smo_block_red<kSmoWaves>(-kSmoInf, bb, bi, shA);
   long long iter = 0;
   double last_gap = 0.0;
   long long ph[5] = {0, 0, 0, 0, 0};
@@ -236,15 +189,13 @@ __global__ __launch_bounds__(kSmoThreads) void smo_kernel(const SmoProb* __restr
     }
   };
   for (; iter < max_iter; ++iter) {
-    const double Gmax = r1.b;
+    const double Gmax = f64_from_okey(r1.kb);
     const int i = r1.idx;
     if (i < 0) break;
     const int yi = i < P.npos ? 1 : -1;
-    // ---- WSS step 2 over row i (second order, libsvm's "last index wins" on ties).  Every
-    // candidate is ranked by the quotient num/quad itself (libsvm's obj_diff, negated exactly), so
-    // the choice never depends on how points are grouped over threads or workgroups.
+    // ---- WSS step 2 over row i (second order, libsvm's "last index wins" on ties)
     const float4* Ki4 = reinterpret_cast<const float4*>(Kp + (size_t)i * P.ld);
-    double gmax2 = -kInf, bkey = -kInf;
+    double gmax2 = -kSmoInf, bkey = -kSmoInf;
     int bj = -1;
     // issue every row-i load before touching any of them: one HBM latency, not K4
     float4 qv[K4];
@@ -261,39 +212,32 @@ __global__ __launch_bounds__(kSmoThreads) void smo_kernel(const SmoProb* __restr
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int k = 4 * g + e;
-        if ((lowm >> k) & 1ull) {
-          const double yG = ((ypos >> k) & 1ull) ? G[k] : -G[k];
+        if ((M.lowm >> k) & 1ull) {
+          const double yG = ((M.ypos >> k) & 1ull) ? G[k] : -G[k];
           gmax2 = fmax(gmax2, yG);
           const double gd = Gmax + yG;
           if (gd > 0) {
-            double quad = 2.0 - 2.0 * (double)Qi[k];
-            if (quad <= 0) quad = kTau;
-            const double key = (gd * gd) / quad;
+            const double key = smo_wss2_key(gd, Qi[k]);
             if (bj < 0 || key >= bkey) { bkey = key; bj = t0 + e; }   // ties → later index
           }
         }
       }
     }
-    Red3 r2{gmax2, bj >= 0 ? bkey : -kInf, bj};
     tick(0);
-    r2 = block_red3(r2, shB);
+    const SmoRedPart r2 = smo_block_red<kSmoWaves>(gmax2, bj >= 0 ? bkey : -kSmoInf, bj, shB);
     tick(1);
     const int j = r2.idx;
-    last_gap = Gmax + r2.a;
-    if (Gmax + r2.a < eps || j < 0) break;
+    const double gmax2_all = f64_from_okey(r2.ka);
+    last_gap = Gmax + gmax2_all;
+    if (Gmax + gmax2_all < eps || j < 0) break;
     // ---- publish α_i (owner of i) and α_j, K_ij, G_j (owner of j); G_i = −y_i·Gmax exactly
     const int oi = (i >> 2) % kSmoThreads, oj = (j >> 2) % kSmoThreads;
     if (tid == oi) pub[0] = alpha[i];
     if (tid == oj) {
       pub[1] = alpha[j];
       const int kk = 4 * ((j >> 2) / kSmoThreads) + (j & 3);
-      float kij = 0.f;
-      double gj = 0.0;
-#pragma unroll
-      for (int k = 0; k < KM; ++k)
-        if (k == kk) { kij = Qi[k]; gj = G[k]; }
-      pub[2] = kij;
-      pub[3] = gj;
+      pub[2] = smo_pick<KM>(Qi, kk);
+      pub[3] = smo_pick<KM>(G, kk);
     }
     __syncthreads();
     const double ai_old = pub[0], aj_old = pub[1];
@@ -301,70 +245,24 @@ __global__ __launch_bounds__(kSmoThreads) void smo_kernel(const SmoProb* __restr
     const double Gj = pub[3];
     const int yj = j < P.npos ? 1 : -1;
     const double Ci = yi > 0 ? P.Cp : P.Cn, Cj = yj > 0 ? P.Cp : P.Cn;
-    const double Qij = (double)(yi * yj) * Kij;
-    const double Gi = -(double)yi * Gmax;
-    double ai = ai_old, aj = aj_old;
-    if (yi != yj) {
-      double quad = 2.0 + 2.0 * Qij;
-      if (quad <= 0) quad = kTau;
-      const double delta = (-Gi - Gj) / quad;
-      const double diff = ai - aj;
-      ai += delta;
-      aj += delta;
-      if (diff > 0) {
-        if (aj < 0) { aj = 0; ai = diff; }
-      } else {
-        if (ai < 0) { ai = 0; aj = -diff; }
-      }
-      if (diff > Ci - Cj) {
-        if (ai > Ci) { ai = Ci; aj = Ci - diff; }
-      } else {
-        if (aj > Cj) { aj = Cj; ai = Cj + diff; }
-      }
-    } else {
-      double quad = 2.0 - 2.0 * Qij;
-      if (quad <= 0) quad = kTau;
-      const double delta = (Gi - Gj) / quad;
-      const double sum = ai + aj;
-      ai -= delta;
-      aj += delta;
-      if (sum > Ci) {
-        if (ai > Ci) { ai = Ci; aj = sum - Ci; }
-      } else {
-        if (aj < 0) { aj = 0; ai = sum; }
-      }
-      if (sum > Cj) {
-        if (aj > Cj) { aj = Cj; ai = sum - Cj; }
-      } else {
-        if (ai < 0) { ai = 0; aj = sum; }
-      }
-    }
-    const double ci = (double)yi * (ai - ai_old), cj = (double)yj * (aj - aj_old);
+    const SmoPair pr = smo_pair_update(yi, yj, Ci, Cj, Kij, Gmax, Gj, ai_old, aj_old);
+    const double ci = pr.ci, cj = pr.cj;
     // owners: store α and refresh the bound masks of i and j
     if (tid == oi || tid == oj) {
 #pragma unroll
       for (int w = 0; w < 2; ++w) {
         const int t = w == 0 ? i : j;
         if ((w == 0 && tid != oi) || (w == 1 && tid != oj)) continue;
-        const double a = w == 0 ? ai : aj;
-        const double C = w == 0 ? Ci : Cj;
+        const double a = w == 0 ? pr.ai : pr.aj;
         alpha[t] = a;
-        const int kk = 4 * ((t >> 2) / kSmoThreads) + (t & 3);
-        const unsigned long long bit = 1ull << kk;
-        const bool pos = (ypos & bit) != 0ull;
-        const bool atU = a >= C, atL = a <= 0;
-        freem = (!atU && !atL) ? (freem | bit) : (freem & ~bit);
-        upperm = atU ? (upperm | bit) : (upperm & ~bit);
-        const bool up = pos ? !atU : !atL;
-        const bool low = pos ? !atL : !atU;
-        upm = up ? (upm | bit) : (upm & ~bit);
-        lowm = low ? (lowm | bit) : (lowm & ~bit);
+        smo_masks_set(M, 1ull << (4 * ((t >> 2) / kSmoThreads) + (t & 3)), a, w == 0 ? Ci : Cj);
       }
     }
     tick(2);
     // ---- fused: gradient update with rows i (registers) and j, then next step-1 candidates
     const float4* Kj4 = reinterpret_cast<const float4*>(Kp + (size_t)j * P.ld);
-    r1 = Red3{-kInf, -kInf, -1};
+    bb = -kSmoInf;
+    bi = -1;
     float4 qjv[K4];
 #pragma unroll
     for (int g = 0; g < K4; ++g)
@@ -377,61 +275,36 @@ __global__ __launch_bounds__(kSmoThreads) void smo_kernel(const SmoProb* __restr
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int k = 4 * g + e;
-        const bool pos = (ypos >> k) & 1ull;
+        const bool pos = (M.ypos >> k) & 1ull;
         const double upd = (double)Qi[k] * ci + (double)qj[e] * cj;
         G[k] += pos ? upd : -upd;
-        if ((upm >> k) & 1ull) red3_combine(r1, -kInf, pos ? -G[k] : G[k], t0 + e);
+        if ((M.upm >> k) & 1ull) smo_arg_take(bb, bi, pos ? -G[k] : G[k], t0 + e);
       }
     }
     tick(3);
-    r1 = block_red3(r1, shA);
+    r1 = smo_block_red<kSmoWaves>(-kSmoInf, bb, bi, shA);
     tick(4);
   }
   if (prof && tid == 0)
     for (int k = 0; k < 5; ++k) out.prof[blockIdx.x * 5 + k] = ph[k];
   // ---- calculate_rho
-  Red3 ru{-kInf, -kInf, -1};   // a = max(−ub)
-  Red3 rl{-kInf, -kInf, -1};   // a = max(lb)
-  double sum_free = 0.0;
+  double ru = -kSmoInf, rl = -kSmoInf, sum_free = 0.0;
   int nfree = 0;
 #pragma unroll
   for (int k = 0; k < KM; ++k) {
     const int t = 4 * (tid + (k >> 2) * kSmoThreads) + (k & 3);
     if (t < P.l) {
-      const bool pos = (ypos >> k) & 1ull;
-      const double yG = pos ? G[k] : -G[k];
-      if ((upperm >> k) & 1ull) {
-        if (!pos) ru.a = fmax(ru.a, -yG); else rl.a = fmax(rl.a, yG);
-      } else if ((freem >> k) & 1ull) {
-        ++nfree;
-        sum_free += yG;
-      } else {
-        if (pos) ru.a = fmax(ru.a, -yG); else rl.a = fmax(rl.a, yG);
-      }
+      const bool pos = (M.ypos >> k) & 1ull;
+      smo_rho_classify(pos, (M.upperm >> k) & 1ull, (M.freem >> k) & 1ull, pos ? G[k] : -G[k], ru, rl, sum_free,
+                       nfree);
     }
   }
-  __syncthreads();   // the loop may exit right after an r1 fold that still reads shA
-  ru = block_red3(ru, shA);
-  rl = block_red3(rl, shB);
-  Red3 rs{-kInf, sum_free, nfree};
-  {
-    // plain sums (not arg-max): reuse the shared buffer with a sum reduction
-    double s = wave_sum(sum_free);
-    double c = wave_sum((double)nfree);
-    const int lane = tid & 63, wave = tid >> 6;
-    __shared__ double ssum[2][kSmoWaves];
-    if (lane == 0) { ssum[0][wave] = s; ssum[1][wave] = c; }
-    __syncthreads();
-    if (tid == 0) {
-      double S = 0, Cc = 0;
-      for (int w = 0; w < kSmoWaves; ++w) { S += ssum[0][w]; Cc += ssum[1][w]; }
-      const double ub = -ru.a, lb = rl.a;
-      out.rho[blockIdx.x] = Cc > 0 ? S / Cc : (ub + lb) / 2;
-      out.iters[blockIdx.x] = (int)iter;
-      out.gap[blockIdx.x] = last_gap;
-    }
+  const SmoRhoPart rp = smo_rho_block<kSmoWaves>(ru, rl, sum_free, nfree, shA, ssum);
+  if (tid == 0) {
+    out.rho[blockIdx.x] = smo_rho_value(-f64_from_okey(rp.kru), f64_from_okey(rp.krl), rp.S, rp.n);
+    out.iters[blockIdx.x] = (int)iter;
+    out.gap[blockIdx.x] = last_gap;
   }
-  (void)rs;
 }
 
 void smo_batch(uintptr_t probs, int P, int max_l, uintptr_t K, uintptr_t alpha, double eps,

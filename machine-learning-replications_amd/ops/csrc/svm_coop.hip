@@ -14,8 +14,8 @@
 // with its own slices of Gram rows i and j (1/W of each row read).
 //
 // Exactness: the reductions are exact max / arg-max (ties → larger index) — independent of
-// how the points are partitioned — and the per-point arithmetic is smo_kernel's (libsvm order,
-// no FMA contraction), so the pair sequence, α and ρ match smo_kernel's.
+// how the points are partitioned — and the per-point arithmetic is smo_kernel's (the steps of
+// smo_steps.h: libsvm order, no FMA contraction), so the pair sequence, α and ρ match smo_kernel's.
 //
 // Liveness: every spin is bounded; a member that times out sets *err and leaves, its peers
 // then time out too and the launch drains (the host raises on err).  The launcher admits at
@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "smo_steps.h"
 
 namespace hfens {
 
@@ -64,8 +65,6 @@ constexpr int kGran = 10;             // granules per member slot
 constexpr int kPkBits = 15;           // Mapped: point key = libsvm index << 15 | column
 constexpr int kPkMask = (1 << kPkBits) - 1;
 constexpr int kMaxMembers = 16;
-constexpr double kCTau = 1e-12;
-constexpr double kCInf = 1.0e300;
 constexpr long long kWaitMsDefault = 20;   // HFENS_SMO_WAIT_MS: per-exchange deadline
 
 // 100 MHz constant-rate counter (independent of the shader clock)
@@ -94,41 +93,6 @@ __device__ __forceinline__ double f64_of(const unsigned* v) {
 }
 __device__ __forceinline__ unsigned long long bits_of(double x) {
   return (unsigned long long)__double_as_longlong(x);
-}
-
-struct CoopPart {
-  unsigned long long ka, kb;
-  int idx, pad;
-};
-
-// Member-local exact reduction (a → max; (b, idx) → arg-max, ties → larger idx): DPP/permlane
-// wave maxima, one barrier, fold of the wave partials.  Every thread receives the result.
-// WantA = false: the caller passes a uniform `a` and ignores the max (WSS step 1), so its two
-// wave-max chains are skipped (the result's ka is then f64_okey(a)).
-template <bool WantA = true>
-__device__ __forceinline__ CoopPart coop_block_red(double a, double b, int idx, CoopPart* sh) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long ka = f64_okey(a), kb = f64_okey(b);
-  unsigned ah = (unsigned)(ka >> 32), al = (unsigned)ka;
-  if constexpr (WantA) {
-    ah = wave_max_u32((unsigned)(ka >> 32));
-    al = wave_max_u32((unsigned)(ka >> 32) == ah ? (unsigned)ka : 0u);
-  }
-  const unsigned bh = wave_max_u32((unsigned)(kb >> 32));
-  const unsigned bl = wave_max_u32((unsigned)(kb >> 32) == bh ? (unsigned)kb : 0u);
-  const bool top = (unsigned)(kb >> 32) == bh && (unsigned)kb == bl;
-  const unsigned bi = wave_max_u32(top ? (unsigned)(idx + 1) : 0u);
-  if (lane == 0)
-    sh[wave] = CoopPart{((unsigned long long)ah << 32) | al, ((unsigned long long)bh << 32) | bl, (int)bi - 1, 0};
-  __syncthreads();
-  CoopPart r = sh[0];
-#pragma unroll
-  for (int w = 1; w < kCoopWaves; ++w) {
-    const CoopPart p = sh[w];
-    r.ka = p.ka > r.ka ? p.ka : r.ka;
-    if (p.kb > r.kb || (p.kb == r.kb && p.idx > r.idx)) { r.kb = p.kb; r.idx = p.idx; }
-  }
-  return r;
 }
 
 // Wave 0 sweeps the first `ng` granules of every member's slot (GS granules per slot) until all
@@ -187,9 +151,123 @@ __device__ __forceinline__ bool coop_gather_t(unsigned long long* slot, int W, i
   return *sh_fail == 0;
 }
 
-__device__ __forceinline__ bool coop_gather(unsigned long long* slot, int W, int ng, unsigned epoch,
-                                            unsigned (*vals)[kGran], const SmoCoopOut& out, int* sh_fail) {
-  return coop_gather_t<kGran>(slot, W, ng, epoch, vals, out, sh_fail);
+// A member's LDS: the alternating reduction partials, the gathered granules of the last two
+// exchanges (GS granules per member slot), the gather's verdict and the ρ sums.
+template <int GS>
+struct CoopLds {
+  SmoRedPart shA[kCoopWaves], shB[kCoopWaves];
+  unsigned vals[2][kMaxMembers][GS];
+  int fail;
+  double ssum[2][kCoopWaves];
+};
+
+// The exchanges of both cooperative kernels (GS = kGran: stored Gram; GS = kOtfGran: the Gram
+// recomputed, whose slots carry the candidate's row behind the common granules).  Slots alternate
+// with the epoch's parity.
+template <int GS>
+__device__ __forceinline__ unsigned long long* coop_slot(unsigned long long* slot0, unsigned epoch) {
+  return slot0 + (size_t)(epoch & 1) * kMaxMembers * GS;
+}
+
+// exchange 1: a member's step-1 partial (kb, idx, α_idx) in granules 0..4
+__device__ __forceinline__ void coop_put1(unsigned long long* mine, unsigned epoch, const SmoRedPart& loc, double a) {
+  put_u64(mine, epoch, loc.kb);
+  put_granule(mine + 2, epoch, (unsigned)loc.idx);
+  put_u64(mine + 3, epoch, bits_of(a));
+}
+
+struct CoopWin1 {
+  unsigned long long kb;   // Gmax key
+  int idx;                 // i
+  double a;                // α_i
+  int m;                   // the member that proposed it
+};
+
+template <int GS>
+__device__ __forceinline__ CoopWin1 coop_fold1(const unsigned (*v)[GS], int W) {
+  CoopWin1 r{u64_of(&v[0][0]), (int)v[0][2], f64_of(&v[0][3]), 0};
+  for (int m = 1; m < W; ++m) {
+    const unsigned long long k2 = u64_of(&v[m][0]);
+    const int i2 = (int)v[m][2];
+    if (k2 > r.kb || (k2 == r.kb && i2 > r.idx)) { r.kb = k2; r.idx = i2; r.a = f64_of(&v[m][3]); r.m = m; }
+  }
+  return r;
+}
+
+// exchange 2: (max yG over I_low, best objective key, j, α_j, G_j, K_ij) in granules 0..9
+__device__ __forceinline__ void coop_put2(unsigned long long* mine, unsigned epoch, const SmoRedPart& loc, double aj,
+                                          double gj, float kij) {
+  put_u64(mine, epoch, loc.ka);
+  put_u64(mine + 2, epoch, loc.kb);
+  put_granule(mine + 4, epoch, (unsigned)loc.idx);
+  put_u64(mine + 5, epoch, bits_of(aj));
+  put_u64(mine + 7, epoch, bits_of(gj));
+  put_granule(mine + 9, epoch, __float_as_uint(kij));
+}
+
+struct CoopWin2 {
+  unsigned long long ka, kb;   // keys of max yG over I_low and of the best objective
+  int j;
+  double aj, Gj, Kij;
+  int m;                       // the member that proposed j
+};
+
+template <int GS>
+__device__ __forceinline__ CoopWin2 coop_fold2(const unsigned (*v)[GS], int W) {
+  CoopWin2 r{u64_of(&v[0][0]), u64_of(&v[0][2]), (int)v[0][4], f64_of(&v[0][5]), f64_of(&v[0][7]),
+             (double)__uint_as_float(v[0][9]), 0};
+  for (int m = 1; m < W; ++m) {
+    const unsigned long long a2 = u64_of(&v[m][0]);
+    r.ka = a2 > r.ka ? a2 : r.ka;
+    const unsigned long long k2 = u64_of(&v[m][2]);
+    const int j2 = (int)v[m][4];
+    if (k2 > r.kb || (k2 == r.kb && j2 > r.j)) {
+      r.kb = k2;
+      r.j = j2;
+      r.aj = f64_of(&v[m][5]);
+      r.Gj = f64_of(&v[m][7]);
+      r.Kij = (double)__uint_as_float(v[m][9]);
+      r.m = m;
+    }
+  }
+  return r;
+}
+
+// calculate_rho over all members: every member's keys of max(−ub) and max(lb) and its free
+// points' sum and count in granules 0..7, folded in member order by member 0, which also writes
+// the iteration count and the gap.
+template <int GS>
+__device__ __forceinline__ void coop_rho_finish(double ru, double rl, double sum_free, int nfree,
+                                                unsigned long long* slot0, unsigned epoch, int p, int w, int W,
+                                                long long iter, double last_gap, CoopLds<GS>& sh,
+                                                const SmoCoopOut& out) {
+#pragma clang fp contract(off)
+  const SmoRhoPart rp = smo_rho_block<kCoopWaves>(ru, rl, sum_free, nfree, sh.shA, sh.ssum);
+  ++epoch;
+  unsigned long long* s3 = coop_slot<GS>(slot0, epoch);
+  if (threadIdx.x == 0) {
+    unsigned long long* mine = s3 + w * GS;
+    put_u64(mine, epoch, rp.kru);       // max(−yG) over the upper-bound candidates
+    put_u64(mine + 2, epoch, rp.krl);   // max(yG) over the lower-bound candidates
+    put_u64(mine + 4, epoch, bits_of(rp.S));
+    put_u64(mine + 6, epoch, bits_of(rp.n));
+  }
+  if (!coop_gather_t<GS>(s3, W, 8, epoch, sh.vals[epoch & 1], out, &sh.fail)) return;
+  if (w == 0 && threadIdx.x == 0) {
+    const unsigned(*v)[GS] = sh.vals[epoch & 1];
+    unsigned long long kru = u64_of(&v[0][0]), krl = u64_of(&v[0][2]);
+    double St = 0.0, Ct = 0.0;
+    for (int m = 0; m < W; ++m) {
+      const unsigned long long a2 = u64_of(&v[m][0]), b2 = u64_of(&v[m][2]);
+      kru = a2 > kru ? a2 : kru;
+      krl = b2 > krl ? b2 : krl;
+      St += f64_of(&v[m][4]);
+      Ct += f64_of(&v[m][6]);
+    }
+    out.rho[p] = smo_rho_value(-f64_from_okey(kru), f64_from_okey(krl), St, Ct);
+    out.iters[p] = (int)iter;
+    out.gap[p] = last_gap;
+  }
 }
 
 // Point ownership inside member w: thread tid, group g < K4, lane-of-vector e < 4 owns column
@@ -228,16 +306,14 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
   const int base = w * Pr.S;
   const int send = min(Pr.lphys, base + Pr.S);   // may be ≤ base: an empty member still exchanges
   unsigned long long* slot0 = xchg + (size_t)p * 2 * kMaxMembers * kGran;
-  __shared__ CoopPart shA[kCoopWaves], shB[kCoopWaves];
-  __shared__ unsigned vals[2][kMaxMembers][kGran];
-  __shared__ int sh_fail;
-  __shared__ double ssum[2][kCoopWaves];
+  __shared__ CoopLds<kGran> sh;
   unsigned epoch = 0;
 
   double G[KM], A[KM];
   float Qi[KM];
   int PK[Mapped ? KM : 1];   // Mapped: key of the point in each slot
-  unsigned long long ypos = 0ull, upm = 0ull, lowm = 0ull, freem = 0ull, upperm = 0ull, validm = 0ull;
+  SmoMasks M;
+  unsigned long long validm = 0ull;
 #pragma unroll
   for (int g = 0; g < K4; ++g)
 #pragma unroll
@@ -254,8 +330,7 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
       }
       if (c < send && t >= 0) {
         validm |= 1ull << k;
-        if (t < Pr.npos) { ypos |= 1ull << k; upm |= 1ull << k; }   // α = 0 is at the lower bound
-        else lowm |= 1ull << k;
+        smo_masks_init(M, 1ull << k, t < Pr.npos);
       }
     }
   // key of slot k (unmapped: its column), and the column and libsvm index of a key
@@ -268,20 +343,6 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
   // (thread, register slot) of the point with key t of this member
   auto owner_thr = [&](int t) { return ((col_of(t) - base) >> 2) % kCoopThreads; };
   auto owner_k = [&](int t) { return 4 * (((col_of(t) - base) >> 2) / kCoopThreads) + ((col_of(t) - base) & 3); };
-  auto pick = [&](const double* arr, int kk) {
-    double v = 0.0;
-#pragma unroll
-    for (int k = 0; k < KM; ++k)
-      if (k == kk) v = arr[k];
-    return v;
-  };
-  auto pickf = [&](const float* arr, int kk) {
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < KM; ++k)
-      if (k == kk) v = arr[k];
-    return v;
-  };
   // While wave 0 polls an exchange, waves 1.. touch one dword per 128-byte line of the FULL Gram
   // row of this member's own candidate: the winning candidate's row — whichever member proposed
   // it — is then in this XCD's L2 (members of a problem share an XCD) when every member reads its
@@ -307,45 +368,35 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
   };
   auto prefetch_retire = [&](const Pf& pf) { asm volatile("" ::"v"(pf.v[0]), "v"(pf.v[1]), "v"(pf.v[2]), "v"(pf.v[3])); };
   // exchange 1: every member's step-1 partial (kb, idx, α_idx) → (Gmax key, i, α_i)
-  auto exchange1 = [&](const CoopPart& loc, unsigned long long& kb, int& idx, double& a_i) -> bool {
+  auto exchange1 = [&](const SmoRedPart& loc, unsigned long long& kb, int& idx, double& a_i) -> bool {
     ++epoch;
-    unsigned long long* s = slot0 + (size_t)(epoch & 1) * kMaxMembers * kGran;
+    unsigned long long* s = coop_slot<kGran>(slot0, epoch);
     const bool has = loc.idx >= 0;
-    if (has ? tid == owner_thr(loc.idx) : tid == 0) {
-      unsigned long long* mine = s + w * kGran;
-      const double av = has ? pick(A, owner_k(loc.idx)) : 0.0;
-      put_u64(mine, epoch, loc.kb);
-      put_granule(mine + 2, epoch, (unsigned)loc.idx);
-      put_u64(mine + 3, epoch, bits_of(av));
-    }
+    if (has ? tid == owner_thr(loc.idx) : tid == 0)
+      coop_put1(s + w * kGran, epoch, loc, has ? smo_pick<KM>(A, owner_k(loc.idx)) : 0.0);
     const Pf pf = prefetch_issue(loc.idx);
-    if (!coop_gather(s, W, 5, epoch, vals[epoch & 1], out, &sh_fail)) return false;
+    if (!coop_gather_t<kGran>(s, W, 5, epoch, sh.vals[epoch & 1], out, &sh.fail)) return false;
     prefetch_retire(pf);
-    const unsigned(*v)[kGran] = vals[epoch & 1];
-    kb = u64_of(&v[0][0]);
-    idx = (int)v[0][2];
-    a_i = f64_of(&v[0][3]);
-    for (int m = 1; m < W; ++m) {
-      const unsigned long long k2 = u64_of(&v[m][0]);
-      const int i2 = (int)v[m][2];
-      if (k2 > kb || (k2 == kb && i2 > idx)) { kb = k2; idx = i2; a_i = f64_of(&v[m][3]); }
-    }
+    const CoopWin1 r = coop_fold1<kGran>(sh.vals[epoch & 1], W);
+    kb = r.kb;
+    idx = r.idx;
+    a_i = r.a;
     return true;
   };
 
   // ---- WSS step 1 for the first iteration
-  CoopPart loc;
+  SmoRedPart loc;
   {
-    double bb = -kCInf;
+    double bb = -kSmoInf;
     int bi = -1;
 #pragma unroll
     for (int k = 0; k < KM; ++k)
-      if ((upm >> k) & 1ull) {
+      if ((M.upm >> k) & 1ull) {
         const int t = key_of(k);
-        const double v = ((ypos >> k) & 1ull) ? -G[k] : G[k];
-        if (v > bb || (v == bb && t > bi)) { bb = v; bi = t; }
+        const double v = ((M.ypos >> k) & 1ull) ? -G[k] : G[k];
+        smo_arg_take(bb, bi, v, t);
       }
-    loc = coop_block_red<false>(-kCInf, bb, bi, shA);
+    loc = smo_block_red<kCoopWaves, false>(-kSmoInf, bb, bi, sh.shA);
   }
   unsigned long long r1kb = 0ull;
   int i = -1;
@@ -369,7 +420,7 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
     const int yi = idx_of(i) < Pr.npos ? 1 : -1;
     // ---- WSS step 2 over this member's slice of row i
     const float4* Ki4 = reinterpret_cast<const float4*>(Kp + (size_t)col_of(i) * Pr.ld + base);
-    double gmax2 = -kCInf, bkey = -kCInf;
+    double gmax2 = -kSmoInf, bkey = -kSmoInf;
     int bj = -1;
     float4 qv[K4];
 #pragma unroll
@@ -383,14 +434,12 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int k = 4 * g + e;
-        if ((lowm >> k) & 1ull) {
-          const double yG = ((ypos >> k) & 1ull) ? G[k] : -G[k];
+        if ((M.lowm >> k) & 1ull) {
+          const double yG = ((M.ypos >> k) & 1ull) ? G[k] : -G[k];
           gmax2 = fmax(gmax2, yG);
           const double gd = Gmax + yG;
           if (gd > 0) {
-            double quad = 2.0 - 2.0 * (double)Qi[k];
-            if (quad <= 0) quad = kCTau;
-            const double key = (gd * gd) / quad;   // smo_kernel's rank: grouping-independent
+            const double key = smo_wss2_key(gd, Qi[k]);
             if constexpr (Mapped) {   // slots are in column order, not index order
               if (bj < 0 || key > bkey || (key == bkey && key_of(k) > bj)) { bkey = key; bj = key_of(k); }
             } else if (bj < 0 || key >= bkey) { bkey = key; bj = t0 + e; }
@@ -399,101 +448,33 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
       }
     }
     tick(0);
-    loc = coop_block_red(gmax2, bj >= 0 ? bkey : -kCInf, bj, shB);
+    loc = smo_block_red<kCoopWaves>(gmax2, bj >= 0 ? bkey : -kSmoInf, bj, sh.shB);
     tick(1);
     // ---- exchange 2: (max yG over I_low, best objective key, j, α_j, G_j, K_ij)
     ++epoch;
-    unsigned long long* s2 = slot0 + (size_t)(epoch & 1) * kMaxMembers * kGran;
+    unsigned long long* s2 = coop_slot<kGran>(slot0, epoch);
     {
       const bool has = loc.idx >= 0;
       if (has ? tid == owner_thr(loc.idx) : tid == 0) {
-        unsigned long long* mine = s2 + w * kGran;
         const int kk = has ? owner_k(loc.idx) : 0;
-        const double aj = has ? pick(A, kk) : 0.0;
-        const double gj = has ? pick(G, kk) : 0.0;
-        const float kij = has ? pickf(Qi, kk) : 0.f;
-        put_u64(mine, epoch, loc.ka);
-        put_u64(mine + 2, epoch, loc.kb);
-        put_granule(mine + 4, epoch, (unsigned)loc.idx);
-        put_u64(mine + 5, epoch, bits_of(aj));
-        put_u64(mine + 7, epoch, bits_of(gj));
-        put_granule(mine + 9, epoch, __float_as_uint(kij));
+        coop_put2(s2 + w * kGran, epoch, loc, has ? smo_pick<KM>(A, kk) : 0.0, has ? smo_pick<KM>(G, kk) : 0.0,
+                  has ? smo_pick<KM>(Qi, kk) : 0.f);
       }
     }
     const Pf pf2 = prefetch_issue(loc.idx);
-    if (!coop_gather(s2, W, 10, epoch, vals[epoch & 1], out, &sh_fail)) return;
+    if (!coop_gather_t<kGran>(s2, W, 10, epoch, sh.vals[epoch & 1], out, &sh.fail)) return;
     prefetch_retire(pf2);
     tick(2);
-    unsigned long long ka2, kb2;
-    int j;
-    double aj_old, Gj, Kij;
-    {
-      const unsigned(*v)[kGran] = vals[epoch & 1];
-      ka2 = u64_of(&v[0][0]);
-      kb2 = u64_of(&v[0][2]);
-      j = (int)v[0][4];
-      aj_old = f64_of(&v[0][5]);
-      Gj = f64_of(&v[0][7]);
-      Kij = (double)__uint_as_float(v[0][9]);
-      for (int m = 1; m < W; ++m) {
-        const unsigned long long a2 = u64_of(&v[m][0]);
-        ka2 = a2 > ka2 ? a2 : ka2;
-        const unsigned long long k2 = u64_of(&v[m][2]);
-        const int j2 = (int)v[m][4];
-        if (k2 > kb2 || (k2 == kb2 && j2 > j)) {
-          kb2 = k2;
-          j = j2;
-          aj_old = f64_of(&v[m][5]);
-          Gj = f64_of(&v[m][7]);
-          Kij = (double)__uint_as_float(v[m][9]);
-        }
-      }
-    }
-    const double gmax2_all = f64_from_okey(ka2);
+    const CoopWin2 r2 = coop_fold2<kGran>(sh.vals[epoch & 1], W);
+    const int j = r2.j;
+    const double gmax2_all = f64_from_okey(r2.ka);
     last_gap = Gmax + gmax2_all;
     if (Gmax + gmax2_all < eps || j < 0) break;
     // ---- pair update (identical in every member)
     const int yj = idx_of(j) < Pr.npos ? 1 : -1;
     const double Ci = yi > 0 ? Pr.Cp : Pr.Cn, Cj = yj > 0 ? Pr.Cp : Pr.Cn;
-    const double Qij = (double)(yi * yj) * Kij;
-    const double Gi = -(double)yi * Gmax;
-    double ai = ai_old, aj = aj_old;
-    if (yi != yj) {
-      double quad = 2.0 + 2.0 * Qij;
-      if (quad <= 0) quad = kCTau;
-      const double delta = (-Gi - Gj) / quad;
-      const double diff = ai - aj;
-      ai += delta;
-      aj += delta;
-      if (diff > 0) {
-        if (aj < 0) { aj = 0; ai = diff; }
-      } else {
-        if (ai < 0) { ai = 0; aj = -diff; }
-      }
-      if (diff > Ci - Cj) {
-        if (ai > Ci) { ai = Ci; aj = Ci - diff; }
-      } else {
-        if (aj > Cj) { aj = Cj; ai = Cj + diff; }
-      }
-    } else {
-      double quad = 2.0 - 2.0 * Qij;
-      if (quad <= 0) quad = kCTau;
-      const double delta = (Gi - Gj) / quad;
-      const double sum = ai + aj;
-      ai -= delta;
-      aj += delta;
-      if (sum > Ci) {
-        if (ai > Ci) { ai = Ci; aj = sum - Ci; }
-      } else {
-        if (aj < 0) { aj = 0; ai = sum; }
-      }
-      if (sum > Cj) {
-        if (aj > Cj) { aj = Cj; ai = sum - Cj; }
-      } else {
-        if (ai < 0) { ai = 0; aj = sum; }
-      }
-    }
-    const double ci = (double)yi * (ai - ai_old), cj = (double)yj * (aj - aj_old);
+    const SmoPair pr = smo_pair_update(yi, yj, Ci, Cj, r2.Kij, Gmax, r2.Gj, ai_old, r2.aj);
+    const double ci = pr.ci, cj = pr.cj;
     tick(3);
     // owners in this member: α and the bound masks of i and j
 #pragma unroll
@@ -501,20 +482,9 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
       const int t = wv == 0 ? i : j;
       if (col_of(t) < base || col_of(t) >= send || tid != owner_thr(t)) continue;
       const int kk = owner_k(t);
-      const double a = wv == 0 ? ai : aj;
-      const double C = wv == 0 ? Ci : Cj;
-#pragma unroll
-      for (int k = 0; k < KM; ++k)
-        if (k == kk) A[k] = a;
-      const unsigned long long bit = 1ull << kk;
-      const bool pos = (ypos & bit) != 0ull;
-      const bool atU = a >= C, atL = a <= 0;
-      freem = (!atU && !atL) ? (freem | bit) : (freem & ~bit);
-      upperm = atU ? (upperm | bit) : (upperm & ~bit);
-      const bool up = pos ? !atU : !atL;
-      const bool low = pos ? !atL : !atU;
-      upm = up ? (upm | bit) : (upm & ~bit);
-      lowm = low ? (lowm | bit) : (lowm & ~bit);
+      const double a = wv == 0 ? pr.ai : pr.aj;
+      smo_put<KM>(A, kk, a);
+      smo_masks_set(M, 1ull << kk, a, wv == 0 ? Ci : Cj);
     }
     // ---- gradient update of this member's slice (row i in registers, row j loaded now), fused
     // with the next step-1 candidates
@@ -523,7 +493,7 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
 #pragma unroll
     for (int g = 0; g < K4; ++g)
       qjv[g] = base + 4 * (tid + g * kCoopThreads) < send ? Kj4[tid + g * kCoopThreads] : make_float4(0.f, 0.f, 0.f, 0.f);
-    double bb = -kCInf;
+    double bb = -kSmoInf;
     int bi = -1;
 #pragma unroll
     for (int g = 0; g < K4; ++g) {
@@ -533,18 +503,18 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int k = 4 * g + e;
-        const bool pos = (ypos >> k) & 1ull;
+        const bool pos = (M.ypos >> k) & 1ull;
         const double upd = (double)Qi[k] * ci + (double)qj[e] * cj;
         G[k] += pos ? upd : -upd;
-        if ((upm >> k) & 1ull) {
+        if ((M.upm >> k) & 1ull) {
           const double v = pos ? -G[k] : G[k];
           const int tk = Mapped ? key_of(k) : t0 + e;
-          if (v > bb || (v == bb && tk > bi)) { bb = v; bi = tk; }
+          smo_arg_take(bb, bi, v, tk);
         }
       }
     }
     tick(4);
-    loc = coop_block_red<false>(-kCInf, bb, bi, shA);
+    loc = smo_block_red<kCoopWaves, false>(-kSmoInf, bb, bi, sh.shA);
     tick(5);
     if (!exchange1(loc, r1kb, i, ai_old)) return;
     tick(6);
@@ -555,57 +525,15 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_kernel(const SmoCoopPro
 #pragma unroll
   for (int k = 0; k < KM; ++k)
     if ((validm >> k) & 1ull) alpha_all[Pr.aoff + idx_of(key_of(k))] = A[k];
-  double ru = -kCInf, rl = -kCInf, sum_free = 0.0;
+  double ru = -kSmoInf, rl = -kSmoInf, sum_free = 0.0;
   int nfree = 0;
 #pragma unroll
   for (int k = 0; k < KM; ++k) {
     if (!((validm >> k) & 1ull)) continue;
-    const bool pos = (ypos >> k) & 1ull;
-    const double yG = pos ? G[k] : -G[k];
-    if ((upperm >> k) & 1ull) {
-      if (!pos) ru = fmax(ru, -yG); else rl = fmax(rl, yG);
-    } else if ((freem >> k) & 1ull) {
-      ++nfree;
-      sum_free += yG;
-    } else {
-      if (pos) ru = fmax(ru, -yG); else rl = fmax(rl, yG);
-    }
+    const bool pos = (M.ypos >> k) & 1ull;
+    smo_rho_classify(pos, (M.upperm >> k) & 1ull, (M.freem >> k) & 1ull, pos ? G[k] : -G[k], ru, rl, sum_free, nfree);
   }
-  __syncthreads();   // the loop may leave right after a fold that still reads shA
-  const CoopPart rr = coop_block_red(ru, rl, -1, shA);
-  {
-    const double s = wave_sum(sum_free), c = wave_sum((double)nfree);
-    if ((tid & 63) == 0) { ssum[0][tid >> 6] = s; ssum[1][tid >> 6] = c; }
-  }
-  __syncthreads();
-  double Sm = 0.0, Cm = 0.0;
-  for (int wv = 0; wv < kCoopWaves; ++wv) { Sm += ssum[0][wv]; Cm += ssum[1][wv]; }
-  ++epoch;
-  unsigned long long* s3 = slot0 + (size_t)(epoch & 1) * kMaxMembers * kGran;
-  if (tid == 0) {
-    unsigned long long* mine = s3 + w * kGran;
-    put_u64(mine, epoch, rr.ka);       // max(−yG) over the upper-bound candidates
-    put_u64(mine + 2, epoch, rr.kb);   // max(yG) over the lower-bound candidates
-    put_u64(mine + 4, epoch, bits_of(Sm));
-    put_u64(mine + 6, epoch, bits_of(Cm));
-  }
-  if (!coop_gather(s3, W, 8, epoch, vals[epoch & 1], out, &sh_fail)) return;
-  if (w == 0 && tid == 0) {
-    const unsigned(*v)[kGran] = vals[epoch & 1];
-    unsigned long long kru = u64_of(&v[0][0]), krl = u64_of(&v[0][2]);
-    double St = 0.0, Ct = 0.0;
-    for (int m = 0; m < W; ++m) {
-      const unsigned long long a2 = u64_of(&v[m][0]), b2 = u64_of(&v[m][2]);
-      kru = a2 > kru ? a2 : kru;
-      krl = b2 > krl ? b2 : krl;
-      St += f64_of(&v[m][4]);
-      Ct += f64_of(&v[m][6]);
-    }
-    const double ub = -f64_from_okey(kru), lb = f64_from_okey(krl);
-    out.rho[p] = Ct > 0 ? St / Ct : (ub + lb) / 2;
-    out.iters[p] = (int)iter;
-    out.gap[p] = last_gap;
-  }
+  coop_rho_finish<kGran>(ru, rl, sum_free, nfree, slot0, epoch, p, w, W, iter, last_gap, sh, out);
 }
 
 // Exchange deadline and the late-member test hook, from the environment (read per launch).
@@ -615,6 +543,26 @@ static void coop_timing(SmoCoopOut& o) {
   const double wait_ms = (w && w[0]) ? std::atof(w) : (double)kWaitMsDefault;
   o.wait_ticks = (long long)(wait_ms * 1e5);               // 100 MHz counter
   o.inject_ticks = (d && d[0]) ? (long long)(std::atof(d) * 1e5) : 0;
+}
+
+// What both cooperative launchers do ahead of the launch: the member and problem counts, the CU
+// bound, the exchange deadline, and the zeroed exchange buffer (`gran` granules per member slot).
+// Returns the block count.
+static unsigned coop_prepare(const char* op, int P, int W, uintptr_t xchg, int gran, SmoCoopOut& o, hipStream_t st) {
+  const std::string name(op);
+  HFENS_REQUIRE(W >= 1 && W <= kMaxMembers, name + ": 1 <= W <= 16 members per problem");
+  HFENS_REQUIRE(P >= 1, name + ": no problems");
+  int dev = 0, ncu = 256;
+  HFENS_CHECK(hipGetDevice(&dev));
+  HFENS_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  // members spin on each other, so all of them must be resident at once: at most one member per
+  // CU (a 512-thread block always fits beside anything else's finished work); the padding
+  // blocks of an incomplete group of 8 problems exit at once
+  HFENS_REQUIRE((long long)P * W <= ncu, name + ": P·W exceeds the CU count (choose a smaller W)");
+  coop_timing(o);
+  // every polled granule starts at epoch 0 (epochs count from 1 within the call)
+  HFENS_CHECK(hipMemsetAsync((void*)xchg, 0, (size_t)P * 2 * kMaxMembers * gran * sizeof(unsigned long long), st));
+  return (unsigned)(8LL * ((P + 7) / 8) * W);
 }
 
 // Members of one problem spin on each other, so all of them must be resident together: the
@@ -633,25 +581,12 @@ void coop_resident_blocks(uintptr_t out) {
 void smo_coop_batch(uintptr_t probs, int P, int W, int max_S, uintptr_t K, uintptr_t maps, uintptr_t alpha,
                     uintptr_t xchg, double eps, long long max_iter, uintptr_t rho, uintptr_t iters, uintptr_t gap,
                     uintptr_t err, uintptr_t prof, uintptr_t stream) {
-  HFENS_REQUIRE(W >= 1 && W <= kMaxMembers, "smo_coop_batch: 1 <= W <= 16 members per problem");
-  HFENS_REQUIRE(P >= 1, "smo_coop_batch: no problems");
   HFENS_REQUIRE(max_S >= 4 && max_S % 4 == 0, "smo_coop_batch: slice must be a positive multiple of 4");
-  int dev = 0, ncu = 256;
-  HFENS_CHECK(hipGetDevice(&dev));
-  HFENS_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  // members spin on each other, so all of them must be resident at once: at most one member per
-  // CU (a 512-thread block always fits beside anything else's finished work); the padding
-  // blocks of an incomplete group of 8 problems exit at once
-  HFENS_REQUIRE((long long)P * W <= ncu, "smo_coop_batch: P·W exceeds the CU count (choose a smaller W)");
-  const int groups = (P + 7) / 8;
-  const long long blocks = 8LL * groups * W;
   const char* pfe = std::getenv("HFENS_SMO_PREFETCH");
   SmoCoopOut o{(double*)rho, (int*)iters, (double*)gap, (unsigned*)err, (long long*)prof,
                (pfe && pfe[0] == '0') ? 0 : 1};
-  coop_timing(o);
   hipStream_t st = as_stream(stream);
-  // every polled granule starts at epoch 0 (epochs count from 1 within the call)
-  HFENS_CHECK(hipMemsetAsync((void*)xchg, 0, (size_t)P * 2 * kMaxMembers * kGran * sizeof(unsigned long long), st));
+  const unsigned blocks = coop_prepare("smo_coop_batch", P, W, xchg, kGran, o, st);
   auto pp = (const SmoCoopProb*)probs;
   auto kp = (const float*)K;
   auto ap = (double*)alpha;
@@ -662,10 +597,10 @@ void smo_coop_batch(uintptr_t probs, int P, int W, int max_S, uintptr_t K, uintp
 #define COOP_CASE(K4)                                                                                           \
   if (max_S <= 4 * K4 * kCoopThreads) {                                                                         \
     if (mp != nullptr)                                                                                          \
-      hipLaunchKernelGGL((smo_coop_kernel<K4, true>), dim3((unsigned)blocks), dim3(kCoopThreads), 0, st, pp, P, \
+      hipLaunchKernelGGL((smo_coop_kernel<K4, true>), dim3(blocks), dim3(kCoopThreads), 0, st, pp, P, \
                          W, kp, mp, ap, xp, eps, max_iter, o);                                                  \
     else                                                                                                        \
-      hipLaunchKernelGGL((smo_coop_kernel<K4, false>), dim3((unsigned)blocks), dim3(kCoopThreads), 0, st, pp,   \
+      hipLaunchKernelGGL((smo_coop_kernel<K4, false>), dim3(blocks), dim3(kCoopThreads), 0, st, pp,   \
                          P, W, kp, mp, ap, xp, eps, max_iter, o);                                               \
     launch_check();                                                                                             \
     return;                                                                                                     \
@@ -723,16 +658,14 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_otf_kernel(const SmoOtf
   const int base = w * Pr.S;
   const int send = min(Pr.l, base + Pr.S);   // may be ≤ base: an empty member still exchanges
   unsigned long long* slot0 = xchg + (size_t)p * 2 * kMaxMembers * kOtfGran;
-  __shared__ CoopPart shA[kCoopWaves], shB[kCoopWaves];
-  __shared__ unsigned vals[2][kMaxMembers][kOtfGran];
-  __shared__ int sh_fail;
-  __shared__ double ssum[2][kCoopWaves];
+  __shared__ CoopLds<kOtfGran> sh;
   unsigned epoch = 0;
 
   float zr[KM][FP], nz[KM];   // this thread's points: rows and squared norms
   double G[KM], A[KM];
   float Qi[KM], Qj[KM];
-  unsigned long long ypos = 0ull, upm = 0ull, lowm = 0ull, freem = 0ull, upperm = 0ull, validm = 0ull;
+  SmoMasks M;
+  unsigned long long validm = 0ull;
 #pragma unroll
   for (int m = 0; m < KM; ++m) {
     const int t = base + tid + kCoopThreads * m;
@@ -751,26 +684,11 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_otf_kernel(const SmoOtf
     Qj[m] = 0.f;
     if (ok) {
       validm |= 1ull << m;
-      if (t < Pr.npos) { ypos |= 1ull << m; upm |= 1ull << m; }   // α = 0 is at the lower bound
-      else lowm |= 1ull << m;
+      smo_masks_init(M, 1ull << m, t < Pr.npos);
     }
   }
   auto owner_thr = [&](int t) { return (t - base) % kCoopThreads; };
   auto owner_m = [&](int t) { return (t - base) / kCoopThreads; };
-  auto pick = [&](const double* arr, int mm) {
-    double v = 0.0;
-#pragma unroll
-    for (int m = 0; m < KM; ++m)
-      if (m == mm) v = arr[m];
-    return v;
-  };
-  auto pickf = [&](const float* arr, int mm) {
-    float v = 0.f;
-#pragma unroll
-    for (int m = 0; m < KM; ++m)
-      if (m == mm) v = arr[m];
-    return v;
-  };
   // this thread's entries of Gram row r; the row's features and norm come from an exchange (LDS)
   auto gram_row = [&](int r, const unsigned* zb, float nzr, float* Qo) {
     float zrow[FP];
@@ -807,45 +725,38 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_otf_kernel(const SmoOtf
     for (int k = 0; k <= F; ++k) put_granule(dst + k, epoch, 0u);
   };
   // exchange 1: (kb, idx, α_idx, ‖z_idx‖², z_idx) → (Gmax key, i, α_i, member holding z_i)
-  auto exchange1 = [&](const CoopPart& loc, unsigned long long& kb, int& idx, double& a_i, int& ms) -> bool {
+  auto exchange1 = [&](const SmoRedPart& loc, unsigned long long& kb, int& idx, double& a_i, int& ms) -> bool {
     ++epoch;
-    unsigned long long* s = slot0 + (size_t)(epoch & 1) * kMaxMembers * kOtfGran;
+    unsigned long long* s = coop_slot<kOtfGran>(slot0, epoch);
     const bool has = loc.idx >= 0;
     if (has ? tid == owner_thr(loc.idx) : tid == 0) {
       unsigned long long* mine = s + w * kOtfGran;
-      put_u64(mine, epoch, loc.kb);
-      put_granule(mine + 2, epoch, (unsigned)loc.idx);
-      put_u64(mine + 3, epoch, bits_of(has ? pick(A, owner_m(loc.idx)) : 0.0));
+      coop_put1(mine, epoch, loc, has ? smo_pick<KM>(A, owner_m(loc.idx)) : 0.0);
       if (has) publish_row(mine + 5, loc.idx);
       else publish_zero_row(mine + 5);
     }
-    if (!coop_gather_t<kOtfGran>(s, W, 6 + F, epoch, vals[epoch & 1], out, &sh_fail)) return false;
-    const unsigned(*v)[kOtfGran] = vals[epoch & 1];
-    kb = u64_of(&v[0][0]);
-    idx = (int)v[0][2];
-    a_i = f64_of(&v[0][3]);
-    ms = 0;
-    for (int m = 1; m < W; ++m) {
-      const unsigned long long k2 = u64_of(&v[m][0]);
-      const int i2 = (int)v[m][2];
-      if (k2 > kb || (k2 == kb && i2 > idx)) { kb = k2; idx = i2; a_i = f64_of(&v[m][3]); ms = m; }
-    }
+    if (!coop_gather_t<kOtfGran>(s, W, 6 + F, epoch, sh.vals[epoch & 1], out, &sh.fail)) return false;
+    const CoopWin1 r = coop_fold1<kOtfGran>(sh.vals[epoch & 1], W);
+    kb = r.kb;
+    idx = r.idx;
+    a_i = r.a;
+    ms = r.m;
     return true;
   };
 
   // ---- WSS step 1 for the first iteration
-  CoopPart loc;
+  SmoRedPart loc;
   {
-    double bb = -kCInf;
+    double bb = -kSmoInf;
     int bi = -1;
 #pragma unroll
     for (int m = 0; m < KM; ++m)
-      if ((upm >> m) & 1ull) {
+      if ((M.upm >> m) & 1ull) {
         const int t = base + tid + kCoopThreads * m;
-        const double v = ((ypos >> m) & 1ull) ? -G[m] : G[m];
-        if (v > bb || (v == bb && t > bi)) { bb = v; bi = t; }
+        const double v = ((M.ypos >> m) & 1ull) ? -G[m] : G[m];
+        smo_arg_take(bb, bi, v, t);
       }
-    loc = coop_block_red<false>(-kCInf, bb, bi, shA);
+    loc = smo_block_red<kCoopWaves, false>(-kSmoInf, bb, bi, sh.shA);
   }
   unsigned long long r1kb = 0ull;
   int i = -1, mi = 0;
@@ -858,230 +769,101 @@ __global__ __launch_bounds__(kCoopThreads) void smo_coop_otf_kernel(const SmoOtf
     const double Gmax = f64_from_okey(r1kb);
     const int yi = i < Pr.npos ? 1 : -1;
     {
-      const unsigned* zb = &vals[epoch & 1][mi][6];
-      gram_row(i, zb, __uint_as_float(vals[epoch & 1][mi][5]), Qi);
+      const unsigned* zb = &sh.vals[epoch & 1][mi][6];
+      gram_row(i, zb, __uint_as_float(sh.vals[epoch & 1][mi][5]), Qi);
     }
     // ---- WSS step 2 over this member's entries of row i
-    double gmax2 = -kCInf, bkey = -kCInf;
+    double gmax2 = -kSmoInf, bkey = -kSmoInf;
     int bj = -1;
 #pragma unroll
     for (int m = 0; m < KM; ++m) {
-      if ((lowm >> m) & 1ull) {
-        const double yG = ((ypos >> m) & 1ull) ? G[m] : -G[m];
+      if ((M.lowm >> m) & 1ull) {
+        const double yG = ((M.ypos >> m) & 1ull) ? G[m] : -G[m];
         gmax2 = fmax(gmax2, yG);
         const double gd = Gmax + yG;
         if (gd > 0) {
-          double quad = 2.0 - 2.0 * (double)Qi[m];
-          if (quad <= 0) quad = kCTau;
-          const double key = (gd * gd) / quad;   // smo_kernel's rank: grouping-independent
+          const double key = smo_wss2_key(gd, Qi[m]);
           if (bj < 0 || key >= bkey) { bkey = key; bj = base + tid + kCoopThreads * m; }
         }
       }
     }
-    loc = coop_block_red(gmax2, bj >= 0 ? bkey : -kCInf, bj, shB);
+    loc = smo_block_red<kCoopWaves>(gmax2, bj >= 0 ? bkey : -kSmoInf, bj, sh.shB);
     // ---- exchange 2: (max yG over I_low, best key, j, α_j, G_j, K_ij, ‖z_j‖², z_j)
     ++epoch;
-    unsigned long long* s2 = slot0 + (size_t)(epoch & 1) * kMaxMembers * kOtfGran;
+    unsigned long long* s2 = coop_slot<kOtfGran>(slot0, epoch);
     {
       const bool has = loc.idx >= 0;
       if (has ? tid == owner_thr(loc.idx) : tid == 0) {
         unsigned long long* mine = s2 + w * kOtfGran;
         const int mm = has ? owner_m(loc.idx) : 0;
-        put_u64(mine, epoch, loc.ka);
-        put_u64(mine + 2, epoch, loc.kb);
-        put_granule(mine + 4, epoch, (unsigned)loc.idx);
-        put_u64(mine + 5, epoch, bits_of(has ? pick(A, mm) : 0.0));
-        put_u64(mine + 7, epoch, bits_of(has ? pick(G, mm) : 0.0));
-        put_granule(mine + 9, epoch, __float_as_uint(has ? pickf(Qi, mm) : 0.f));
+        coop_put2(mine, epoch, loc, has ? smo_pick<KM>(A, mm) : 0.0, has ? smo_pick<KM>(G, mm) : 0.0,
+                  has ? smo_pick<KM>(Qi, mm) : 0.f);
         if (has) publish_row(mine + 10, loc.idx);
         else publish_zero_row(mine + 10);
       }
     }
-    if (!coop_gather_t<kOtfGran>(s2, W, 11 + F, epoch, vals[epoch & 1], out, &sh_fail)) return;
-    unsigned long long ka2, kb2;
-    int j, mj;
-    double aj_old, Gj, Kij;
-    {
-      const unsigned(*v)[kOtfGran] = vals[epoch & 1];
-      ka2 = u64_of(&v[0][0]);
-      kb2 = u64_of(&v[0][2]);
-      j = (int)v[0][4];
-      aj_old = f64_of(&v[0][5]);
-      Gj = f64_of(&v[0][7]);
-      Kij = (double)__uint_as_float(v[0][9]);
-      mj = 0;
-      for (int m = 1; m < W; ++m) {
-        const unsigned long long a2 = u64_of(&v[m][0]);
-        ka2 = a2 > ka2 ? a2 : ka2;
-        const unsigned long long k2 = u64_of(&v[m][2]);
-        const int j2 = (int)v[m][4];
-        if (k2 > kb2 || (k2 == kb2 && j2 > j)) {
-          kb2 = k2;
-          j = j2;
-          aj_old = f64_of(&v[m][5]);
-          Gj = f64_of(&v[m][7]);
-          Kij = (double)__uint_as_float(v[m][9]);
-          mj = m;
-        }
-      }
-    }
-    const double gmax2_all = f64_from_okey(ka2);
+    if (!coop_gather_t<kOtfGran>(s2, W, 11 + F, epoch, sh.vals[epoch & 1], out, &sh.fail)) return;
+    const CoopWin2 r2 = coop_fold2<kOtfGran>(sh.vals[epoch & 1], W);
+    const int j = r2.j, mj = r2.m;
+    const double gmax2_all = f64_from_okey(r2.ka);
     last_gap = Gmax + gmax2_all;
     if (Gmax + gmax2_all < eps || j < 0) break;
     // ---- pair update (identical in every member; libsvm's clipping)
     const int yj = j < Pr.npos ? 1 : -1;
     const double Ci = yi > 0 ? Pr.Cp : Pr.Cn, Cj = yj > 0 ? Pr.Cp : Pr.Cn;
-    const double Qij = (double)(yi * yj) * Kij;
-    const double Gi = -(double)yi * Gmax;
-    double ai = ai_old, aj = aj_old;
-    if (yi != yj) {
-      double quad = 2.0 + 2.0 * Qij;
-      if (quad <= 0) quad = kCTau;
-      const double delta = (-Gi - Gj) / quad;
-      const double diff = ai - aj;
-      ai += delta;
-      aj += delta;
-      if (diff > 0) {
-        if (aj < 0) { aj = 0; ai = diff; }
-      } else {
-        if (ai < 0) { ai = 0; aj = -diff; }
-      }
-      if (diff > Ci - Cj) {
-        if (ai > Ci) { ai = Ci; aj = Ci - diff; }
-      } else {
-        if (aj > Cj) { aj = Cj; ai = Cj + diff; }
-      }
-    } else {
-      double quad = 2.0 - 2.0 * Qij;
-      if (quad <= 0) quad = kCTau;
-      const double delta = (Gi - Gj) / quad;
-      const double sum = ai + aj;
-      ai -= delta;
-      aj += delta;
-      if (sum > Ci) {
-        if (ai > Ci) { ai = Ci; aj = sum - Ci; }
-      } else {
-        if (aj < 0) { aj = 0; ai = sum; }
-      }
-      if (sum > Cj) {
-        if (aj > Cj) { aj = Cj; ai = sum - Cj; }
-      } else {
-        if (ai < 0) { ai = 0; aj = sum; }
-      }
-    }
-    const double ci = (double)yi * (ai - ai_old), cj = (double)yj * (aj - aj_old);
+    const SmoPair pr = smo_pair_update(yi, yj, Ci, Cj, r2.Kij, Gmax, r2.Gj, ai_old, r2.aj);
+    const double ci = pr.ci, cj = pr.cj;
 #pragma unroll
     for (int wv = 0; wv < 2; ++wv) {
       const int t = wv == 0 ? i : j;
       if (t < base || t >= send || tid != owner_thr(t)) continue;
       const int mm = owner_m(t);
-      const double a = wv == 0 ? ai : aj;
-      const double C = wv == 0 ? Ci : Cj;
-#pragma unroll
-      for (int m = 0; m < KM; ++m)
-        if (m == mm) A[m] = a;
-      const unsigned long long bit = 1ull << mm;
-      const bool pos = (ypos & bit) != 0ull;
-      const bool atU = a >= C, atL = a <= 0;
-      freem = (!atU && !atL) ? (freem | bit) : (freem & ~bit);
-      upperm = atU ? (upperm | bit) : (upperm & ~bit);
-      const bool up = pos ? !atU : !atL;
-      const bool low = pos ? !atL : !atU;
-      upm = up ? (upm | bit) : (upm & ~bit);
-      lowm = low ? (lowm | bit) : (lowm & ~bit);
+      const double a = wv == 0 ? pr.ai : pr.aj;
+      smo_put<KM>(A, mm, a);
+      smo_masks_set(M, 1ull << mm, a, wv == 0 ? Ci : Cj);
     }
     // ---- gradient update with rows i (registers) and j (recomputed now), fused with the next
     // step-1 candidates
-    gram_row(j, &vals[epoch & 1][mj][11], __uint_as_float(vals[epoch & 1][mj][10]), Qj);
-    double bb = -kCInf;
+    gram_row(j, &sh.vals[epoch & 1][mj][11], __uint_as_float(sh.vals[epoch & 1][mj][10]), Qj);
+    double bb = -kSmoInf;
     int bi = -1;
 #pragma unroll
     for (int m = 0; m < KM; ++m) {
-      const bool pos = (ypos >> m) & 1ull;
+      const bool pos = (M.ypos >> m) & 1ull;
       const double upd = (double)Qi[m] * ci + (double)Qj[m] * cj;
       G[m] += pos ? upd : -upd;
-      if ((upm >> m) & 1ull) {
+      if ((M.upm >> m) & 1ull) {
         const int t = base + tid + kCoopThreads * m;
         const double v = pos ? -G[m] : G[m];
-        if (v > bb || (v == bb && t > bi)) { bb = v; bi = t; }
+        smo_arg_take(bb, bi, v, t);
       }
     }
-    loc = coop_block_red<false>(-kCInf, bb, bi, shA);
+    loc = smo_block_red<kCoopWaves, false>(-kSmoInf, bb, bi, sh.shA);
     if (!exchange1(loc, r1kb, i, ai_old, mi)) return;
   }
   // ---- α out (owners) and calculate_rho over all members
 #pragma unroll
   for (int m = 0; m < KM; ++m)
     if ((validm >> m) & 1ull) alpha_all[Pr.aoff + base + tid + kCoopThreads * m] = A[m];
-  double ru = -kCInf, rl = -kCInf, sum_free = 0.0;
+  double ru = -kSmoInf, rl = -kSmoInf, sum_free = 0.0;
   int nfree = 0;
 #pragma unroll
   for (int m = 0; m < KM; ++m) {
     if (!((validm >> m) & 1ull)) continue;
-    const bool pos = (ypos >> m) & 1ull;
-    const double yG = pos ? G[m] : -G[m];
-    if ((upperm >> m) & 1ull) {
-      if (!pos) ru = fmax(ru, -yG); else rl = fmax(rl, yG);
-    } else if ((freem >> m) & 1ull) {
-      ++nfree;
-      sum_free += yG;
-    } else {
-      if (pos) ru = fmax(ru, -yG); else rl = fmax(rl, yG);
-    }
+    const bool pos = (M.ypos >> m) & 1ull;
+    smo_rho_classify(pos, (M.upperm >> m) & 1ull, (M.freem >> m) & 1ull, pos ? G[m] : -G[m], ru, rl, sum_free, nfree);
   }
-  __syncthreads();   // the loop may leave right after a fold that still reads shA
-  const CoopPart rr = coop_block_red(ru, rl, -1, shA);
-  {
-    const double sm = wave_sum(sum_free), c = wave_sum((double)nfree);
-    if ((tid & 63) == 0) { ssum[0][tid >> 6] = sm; ssum[1][tid >> 6] = c; }
-  }
-  __syncthreads();
-  double Sm = 0.0, Cm = 0.0;
-  for (int wv = 0; wv < kCoopWaves; ++wv) { Sm += ssum[0][wv]; Cm += ssum[1][wv]; }
-  ++epoch;
-  unsigned long long* s3 = slot0 + (size_t)(epoch & 1) * kMaxMembers * kOtfGran;
-  if (tid == 0) {
-    unsigned long long* mine = s3 + w * kOtfGran;
-    put_u64(mine, epoch, rr.ka);
-    put_u64(mine + 2, epoch, rr.kb);
-    put_u64(mine + 4, epoch, bits_of(Sm));
-    put_u64(mine + 6, epoch, bits_of(Cm));
-  }
-  if (!coop_gather_t<kOtfGran>(s3, W, 8, epoch, vals[epoch & 1], out, &sh_fail)) return;
-  if (w == 0 && tid == 0) {
-    const unsigned(*v)[kOtfGran] = vals[epoch & 1];
-    unsigned long long kru = u64_of(&v[0][0]), krl = u64_of(&v[0][2]);
-    double St = 0.0, Ct = 0.0;
-    for (int m = 0; m < W; ++m) {
-      const unsigned long long a2 = u64_of(&v[m][0]), b2 = u64_of(&v[m][2]);
-      kru = a2 > kru ? a2 : kru;
-      krl = b2 > krl ? b2 : krl;
-      St += f64_of(&v[m][4]);
-      Ct += f64_of(&v[m][6]);
-    }
-    const double ub = -f64_from_okey(kru), lb = f64_from_okey(krl);
-    out.rho[p] = Ct > 0 ? St / Ct : (ub + lb) / 2;
-    out.iters[p] = (int)iter;
-    out.gap[p] = last_gap;
-  }
+  coop_rho_finish<kOtfGran>(ru, rl, sum_free, nfree, slot0, epoch, p, w, W, iter, last_gap, sh, out);
 }
 
 void smo_coop_otf_batch(uintptr_t probs, int P, int W, int F, int max_S, uintptr_t zcat, uintptr_t alpha,
                         uintptr_t xchg, double eps, long long max_iter, uintptr_t rho, uintptr_t iters,
                         uintptr_t gap, uintptr_t err, uintptr_t stream) {
-  HFENS_REQUIRE(W >= 1 && W <= kMaxMembers, "smo_coop_otf_batch: 1 <= W <= 16 members per problem");
-  HFENS_REQUIRE(P >= 1, "smo_coop_otf_batch: no problems");
   HFENS_REQUIRE(F >= 1 && F <= kOtfMaxF, "smo_coop_otf_batch: 1 <= F <= 20 (rows held in registers)");
   HFENS_REQUIRE(max_S >= 1 && max_S <= 4 * kCoopThreads, "smo_coop_otf_batch: at most 2048 points per member");
-  int dev = 0, ncu = 256;
-  HFENS_CHECK(hipGetDevice(&dev));
-  HFENS_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  HFENS_REQUIRE((long long)P * W <= ncu, "smo_coop_otf_batch: P·W exceeds the CU count (choose a smaller W)");
-  const long long blocks = 8LL * ((P + 7) / 8) * W;
   SmoCoopOut o{(double*)rho, (int*)iters, (double*)gap, (unsigned*)err, nullptr};
-  coop_timing(o);
   hipStream_t st = as_stream(stream);
-  HFENS_CHECK(hipMemsetAsync((void*)xchg, 0, (size_t)P * 2 * kMaxMembers * kOtfGran * sizeof(unsigned long long), st));
+  const unsigned blocks = coop_prepare("smo_coop_otf_batch", P, W, xchg, kOtfGran, o, st);
   auto pp = (const SmoOtfProb*)probs;
   auto zp = (const float*)zcat;
   auto ap = (double*)alpha;
@@ -1089,7 +871,7 @@ void smo_coop_otf_batch(uintptr_t probs, int P, int W, int F, int max_S, uintptr
   const int KM = (max_S + kCoopThreads - 1) / kCoopThreads;
 #define OTF_CASE(KM_, FP_)                                                                                   \
   if (KM <= KM_ && F <= FP_) {                                                                               \
-    hipLaunchKernelGGL((smo_coop_otf_kernel<KM_, FP_>), dim3((unsigned)blocks), dim3(kCoopThreads), 0, st, pp, \
+    hipLaunchKernelGGL((smo_coop_otf_kernel<KM_, FP_>), dim3(blocks), dim3(kCoopThreads), 0, st, pp, \
                        P, W, F, zp, ap, xp, eps, max_iter, o);                                              \
     launch_check();                                                                                          \
     return;                                                                                                  \

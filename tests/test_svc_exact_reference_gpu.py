@@ -163,9 +163,9 @@ def _check_solution(p, alpha, rho, iters, gap, Kh=None, o=None, npos=None):
     assert kkt["gap"] < C.EPS + 2 * o.drift.max(), (float(kkt["gap"]), o.drift.max())
 
 
-@pytest.mark.parametrize("kind,l", SMO_CASES, ids=lambda v: str(v))
-def test_smo_batch(dev, kind, l):
-    p = _problem(dev, kind, l)
+def _smo_launch(dev, p, max_l=None):
+    """One smo_batch launch on the problem's device Gram; ``max_l`` (default: the problem's own size)
+    picks the smo_kernel<K4> instantiation.  α with its 64 guard entries, ρ, iterations, gap."""
     l = p["l"]
     sm = np.zeros(1, smo._SMO_DT)
     sm[0] = (0, 0, l, p["ld"], p["npos"], 0, p["Cp"], p["Cn"])
@@ -173,16 +173,35 @@ def test_smo_batch(dev, kind, l):
     rho = torch.zeros(1, dtype=torch.float64, device=dev)
     iters = torch.zeros(1, dtype=torch.int32, device=dev)
     gap = torch.zeros(1, dtype=torch.float64, device=dev)
-    _E().smo_batch(_tab(sm, dev).data_ptr(), 1, l, p["K"].data_ptr(), alpha.data_ptr(), C.EPS, C.MAX_ITER,
-                   rho.data_ptr(), iters.data_ptr(), gap.data_ptr(), 0, _s(dev))
-    a = alpha.cpu().numpy()
+    _E().smo_batch(_tab(sm, dev).data_ptr(), 1, l if max_l is None else max_l, p["K"].data_ptr(), alpha.data_ptr(),
+                   C.EPS, C.MAX_ITER, rho.data_ptr(), iters.data_ptr(), gap.data_ptr(), 0, _s(dev))
+    return alpha.cpu().numpy(), float(rho.item()), int(iters.item()), float(gap.item())
+
+
+@pytest.mark.parametrize("kind,l", SMO_CASES, ids=lambda v: str(v))
+def test_smo_batch(dev, kind, l):
+    p = _problem(dev, kind, l)
+    l = p["l"]
+    a, rho, iters, gap = _smo_launch(dev, p)
     assert (a[l:] == -7.0).all()
-    _check_solution(p, a[:l].copy(), float(rho.item()), int(iters.item()), float(gap.item()))
+    _check_solution(p, a[:l].copy(), rho, iters, gap)
     if kind == "all_bound":
         assert (a[:l] == np.where(np.arange(l) < p["npos"], p["Cp"], p["Cn"])).all()     # the no-free-vector ρ
 
 
-def _coop_launch(dev, K, l, ld, npos, Cp, Cn, W, S, lphys=None, cmap=None):
+@pytest.mark.parametrize("max_l", [4096, 8192, 12288, 16384, 24576, 32768])
+def test_smo_batch_every_bucket(dev, max_l):
+    """smo_batch picks smo_kernel<K4> from max_l, not from the problem: K4 = 1, 2, 3, 4, 6, 8 (the last
+    three spill) on one 257-point problem, where all but the first register group of every thread is
+    empty."""
+    p = _problem(dev, "gauss", 257)
+    l = p["l"]
+    a, rho, iters, gap = _smo_launch(dev, p, max_l=max_l)
+    assert (a[l:] == -7.0).all()
+    _check_solution(p, a[:l].copy(), rho, iters, gap)
+
+
+def _coop_launch(dev, K, l, ld, npos, Cp, Cn, W, S, lphys=None, cmap=None, max_S=None):
     cp = np.zeros(1, smo._COOP_DT)
     lphys = l if lphys is None else lphys
     cp[0] = (0, 0, 0 if cmap is not None else -1, l, ld, npos, S, lphys, 0, Cp, Cn)
@@ -194,7 +213,8 @@ def _coop_launch(dev, K, l, ld, npos, Cp, Cn, W, S, lphys=None, cmap=None):
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     mdev = _d(cmap.astype(np.int32), dev) if cmap is not None else None
     assert 1 * W <= 16                       # P·W ≤ 16: co-resident by construction
-    _E().smo_coop_batch(_tab(cp, dev).data_ptr(), 1, W, S, K.data_ptr(), mdev.data_ptr() if mdev is not None else 0,
+    _E().smo_coop_batch(_tab(cp, dev).data_ptr(), 1, W, S if max_S is None else max_S, K.data_ptr(),
+                        mdev.data_ptr() if mdev is not None else 0,
                         alpha.data_ptr(), xchg.data_ptr(), C.EPS, C.MAX_ITER, rho.data_ptr(), iters.data_ptr(),
                         gap.data_ptr(), err.data_ptr(), 0, _s(dev))
     e = int(err.item())
@@ -217,9 +237,7 @@ def test_smo_coop_empty_member(dev):
     _check_solution(p, *_coop_launch(dev, p["K"], 9, p["ld"], p["npos"], p["Cp"], p["Cn"], 4, 4))
 
 
-def test_smo_coop_mapped_submatrix(dev):
-    """A sub-problem reads its parent's Gram through a column map; W = 3, S = 16 over 48 parent
-    columns, and the sub-problem leaves out columns 16..31: member 1's whole slice maps to −1."""
+def _mapped_submatrix(dev, max_S=None):
     p = _problem(dev, "gauss", 48)
     keep = np.r_[0:16, 32:48]
     cmap = np.full(48, -1, np.int32)
@@ -227,9 +245,81 @@ def test_smo_coop_mapped_submatrix(dev):
     npos = int((keep < p["npos"]).sum())
     assert 0 < npos < keep.size
     Ksub = p["Kh"][np.ix_(keep, keep)]
-    o = R.smo_oracle(Ksub, npos, p["Cp"], p["Cn"], C.EPS, C.MAX_ITER)
-    got = _coop_launch(dev, p["K"], keep.size, p["ld"], npos, p["Cp"], p["Cn"], 3, 16, lphys=48, cmap=cmap)
-    _check_solution(p, *got, Kh=Ksub, o=o, npos=npos)
+    if "o_sub" not in p:
+        p["o_sub"] = R.smo_oracle(Ksub, npos, p["Cp"], p["Cn"], C.EPS, C.MAX_ITER)
+    got = _coop_launch(dev, p["K"], keep.size, p["ld"], npos, p["Cp"], p["Cn"], 3, 16, lphys=48, cmap=cmap,
+                       max_S=max_S)
+    _check_solution(p, *got, Kh=Ksub, o=p["o_sub"], npos=npos)
+
+
+def test_smo_coop_mapped_submatrix(dev):
+    """A sub-problem reads its parent's Gram through a column map; W = 3, S = 16 over 48 parent
+    columns, and the sub-problem leaves out columns 16..31: member 1's whole slice maps to −1."""
+    _mapped_submatrix(dev)
+
+
+@pytest.mark.parametrize("mapped", [False, True], ids=["unmapped", "mapped"])
+@pytest.mark.parametrize("max_S", [2048, 4096, 8192, 16384])
+def test_smo_coop_every_bucket(dev, max_S, mapped):
+    """smo_coop_batch picks smo_coop_kernel<K4, Mapped> from max_S: K4 = 1, 2, 4, 8 (the last spills),
+    unmapped on 257 points over 3 members and mapped on the 48-column sub-problem above."""
+    if mapped:
+        _mapped_submatrix(dev, max_S=max_S)
+        return
+    p = _problem(dev, "gauss", 257)
+    l = p["l"]
+    S = -(-(-(-l // 3)) // 4) * 4
+    _check_solution(p, *_coop_launch(dev, p["K"], l, p["ld"], p["npos"], p["Cp"], p["Cn"], 3, S, max_S=max_S))
+
+
+def _otf_launch(dev, Z, l, npos, Cp, Cn, e2, W, S, max_S=None):
+    """One smo_coop_otf_batch launch on the rows Z; ``max_S`` (default S) picks the points-per-thread
+    bucket of smo_coop_otf_kernel<KM, FP>, the width of Z the feature bucket."""
+    F = Z.shape[1]
+    op = np.zeros(1, smo._OTF_DT)
+    op[0] = (0, 0, l, npos, S, e2, Cp, Cn)
+    alpha = torch.full((l + 64,), -7.0, dtype=torch.float64, device=dev)
+    rho = torch.zeros(1, dtype=torch.float64, device=dev)
+    iters = torch.zeros(1, dtype=torch.int32, device=dev)
+    gap = torch.zeros(1, dtype=torch.float64, device=dev)
+    xchg = torch.empty(smo._OTF_GRANULES, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _E().smo_coop_otf_batch(_tab(op, dev).data_ptr(), 1, W, F, S if max_S is None else max_S, _d(Z, dev).data_ptr(),
+                            alpha.data_ptr(), xchg.data_ptr(), C.EPS, C.MAX_ITER, rho.data_ptr(), iters.data_ptr(),
+                            gap.data_ptr(), err.data_ptr(), _s(dev))
+    e = int(err.item())
+    assert e == 0, f"smo_coop_otf_batch raised err = {e}: a member exchange timed out (not retried)"
+    a = alpha.cpu().numpy()
+    assert (a[l:] == -7.0).all()
+    return a[:l].copy(), float(rho.item()), int(iters.item()), float(gap.item())
+
+
+@pytest.mark.parametrize("F", [5, 17])
+@pytest.mark.parametrize("max_S", [512, 1024, 2048])
+def test_smo_coop_otf_follows_stored_gram(dev, max_S, F):
+    """The on-the-fly kernel's contract: it re-evaluates gram_rbf_kernel's expression, so it takes the
+    pairs of the stored-Gram solvers on the device Gram of the same rows — the same iteration count
+    and bit-equal α as smo_batch.  255 points of F features over W = 2 members (S = 128), in every
+    instantiation: max_S gives KM = 1, 2, 4 points per thread, F = 5 / 17 the feature tiles 8 / 20."""
+    key = ("otf_rows", F)
+    if key not in _cache:
+        Z, npos, Cp, Cn = C.smo_problem("gauss", 255, F=F)
+        l = Z.shape[0]
+        e2 = C.ngl2e_of(F)
+        ld = _ld(l)
+        g = np.zeros(1, smo._GRAM_DT)
+        g[0] = (0, 0, l, ld, e2, 0)
+        K = torch.full((l * ld,), float("nan"), dtype=torch.float32, device=dev)
+        _E().gram_rbf_batch(_d(Z, dev).data_ptr(), F, _tab(g, dev).data_ptr(), 1, l, K.data_ptr(), _s(dev))
+        p = dict(Z=Z, npos=npos, Cp=Cp, Cn=Cn, l=l, ld=ld, e2=e2, K=K)
+        a, rho, iters, gap = _smo_launch(dev, p)
+        _cache[key] = dict(p, ref=(a[:l].copy(), iters))
+    p = _cache[key]
+    a, rho, iters, gap = _otf_launch(dev, p["Z"], p["l"], p["npos"], p["Cp"], p["Cn"], p["e2"], 2, 128, max_S=max_S)
+    ra, riters = p["ref"]
+    assert riters > 0
+    assert iters == riters, (iters, riters)
+    assert np.array_equal(a.view(np.uint64), ra.view(np.uint64)), int((a != ra).sum())
 
 
 @pytest.mark.parametrize("kind,l,W", [("gauss", 255, 2), ("gauss", 1025, 3)])
@@ -242,33 +332,18 @@ def test_smo_coop_otf_true_kernel_certificate(dev, kind, l, W):
     iteration count: one update rounds five times (smo_oracle's docstring), with |K̂| ≤ 1,
     |Δα| ≤ Cmax and |G_t| ≤ 1 + Σ_c C_c, by at most 2⁻⁵³·(1 + 2⁻⁵⁰)·(6·Cmax + 1 + Σ_c C_c)."""
     p = _problem(dev, kind, l)
-    Z, F = p["Z"], p["Z"].shape[1]
-    S = -(-l // W)
-    op = np.zeros(1, smo._OTF_DT)
-    op[0] = (0, 0, l, p["npos"], S, p["e2"], p["Cp"], p["Cn"])
-    alpha = torch.full((l + 64,), -7.0, dtype=torch.float64, device=dev)
-    rho = torch.zeros(1, dtype=torch.float64, device=dev)
-    iters = torch.zeros(1, dtype=torch.int32, device=dev)
-    gap = torch.zeros(1, dtype=torch.float64, device=dev)
-    xchg = torch.empty(smo._OTF_GRANULES, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _E().smo_coop_otf_batch(_tab(op, dev).data_ptr(), 1, W, F, S, _d(Z, dev).data_ptr(), alpha.data_ptr(),
-                            xchg.data_ptr(), C.EPS, C.MAX_ITER, rho.data_ptr(), iters.data_ptr(), gap.data_ptr(),
-                            err.data_ptr(), _s(dev))
-    e = int(err.item())
-    assert e == 0, f"smo_coop_otf_batch raised err = {e}: a member exchange timed out (not retried)"
-    a = alpha.cpu().numpy()[:l].copy()
+    Z = p["Z"]
+    a, rho_v, it, _ = _otf_launch(dev, Z, l, p["npos"], p["Cp"], p["Cn"], p["e2"], W, -(-l // W))
     Cv = np.where(np.arange(l) < p["npos"], p["Cp"], p["Cn"])
     assert ((a >= 0) & (a <= Cv)).all()
     o = R.svc_dual_oracle(Z, p["npos"], p["Cp"], p["Cn"], p["e2"], a)
     _, dK = R.gram_kernel_error(Z, p["e2"])
-    it = int(iters.item())
     drift = it * U64 * (1 + 2.0 ** -50) * (6 * max(p["Cp"], p["Cn"]) + 1 + Cv.sum())
     budget = float((dK @ a.astype(L)).max()) + drift
     print(f"otf {kind} {l} W={W}: true gap {float(o['gap']):.4e} budget {budget:.3e} "
-          f"drift {drift:.2e} iters {it} rho diff {float(abs(L(rho.item()) - o['rho'])):.3e}")
+          f"drift {drift:.2e} iters {it} rho diff {float(abs(L(rho_v) - o['rho'])):.3e}")
     assert o["gap"] < C.EPS + 2 * budget, (float(o["gap"]), budget)
-    assert abs(L(rho.item()) - o["rho"]) <= budget, (rho.item(), float(o["rho"]), budget)
+    assert abs(L(rho_v) - o["rho"]) <= budget, (rho_v, float(o["rho"]), budget)
 
 
 # ------------------------------------------------------------------------------------ svm_sv_compact
