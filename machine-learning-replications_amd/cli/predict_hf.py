@@ -6,6 +6,7 @@ shipped example patient and the probability is printed between ``#`` rules.
 Additions: ``--set NAME=VALUE`` overrides, ``--csv`` batched scoring, ``--device``
 (``cuda`` runs the gfx950 kernels), ``--model`` path, ``--explain [--background CSV]``
 (exact Shapley contribution of every variable, printed after the unchanged probability block),
+``--explain-pairs [N]`` (the patient's N strongest variable pairs by exact Shapley interaction value),
 ``--what-if [NAMES]`` / ``--what-if-csv PATH`` (the patient's risk as one variable moves over its
 grid, everything else as entered) and ``--interactions [N]`` (Friedman's H² of variable pairs).
 """
@@ -80,6 +81,31 @@ def format_importance(names, mean_abs) -> str:
     return "\n".join(lines)
 
 
+def format_pairs(e, top: int, p: int = 0) -> str:
+    """The ``top`` strongest pairs of row ``p`` (names, pair effect ``2·Phi_ij`` in percentage points), then
+    the sum check: main effects (the diagonal) plus all pair effects = prediction − base."""
+    lines = ["Strongest variable pairs for this patient (pair effect 2*Phi_ij, percentage points):"]
+    for i, j, eff in e.top(top, p):
+        lines.append(f"  {e.feature_names[i]:<24s} {e.feature_names[j]:<24s} {100 * eff:+10.4f}")
+    m = e.Phi[p].cpu()
+    main = float(torch.diag(m).sum())
+    pair = float(torch.triu(m, 1).sum()) * 2.0
+    pred, base = float(e.prediction[p]), e.base_value
+    lines.append(f"Main effects {100 * main:+.4f} + pair effects {100 * pair:+.4f} = {100 * (main + pair):+.4f}"
+                 f" = {100 * pred:.4f} - {100 * base:.4f}")
+    return "\n".join(lines)
+
+
+def format_pair_importance(e, top: int) -> str:
+    m = e.mean_abs_pairs().cpu()
+    F = m.shape[0]
+    pairs = sorted(((i, j, float(m[i, j])) for i in range(F) for j in range(i + 1, F)), key=lambda t: -t[2])
+    lines = ["Mean |pair effect| of variable pairs over the cohort (percentage points, strongest first):"]
+    for i, j, eff in pairs[:top]:
+        lines.append(f"  {e.feature_names[i]:<24s} {e.feature_names[j]:<24s} {100 * eff:10.4f}")
+    return "\n".join(lines)
+
+
 def format_what_if(w, p: int = 0) -> str:
     """One line per variable (current value, risk now, lowest and highest risk along the grid and
     where), sorted by ``highest − lowest``, descending."""
@@ -120,8 +146,11 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default="cpu")
     ap.add_argument("--explain", action="store_true",
                     help="exact Shapley contribution of every variable (with --csv: mean |contribution|)")
+    ap.add_argument("--explain-pairs", nargs="?", const=10, default=None, type=int, metavar="N",
+                    help="after the --explain block (which it implies), the N (default 10) strongest variable "
+                         "pairs by exact Shapley interaction value (with --csv: mean |pair effect|)")
     ap.add_argument("--background", default=None, metavar="CSV",
-                    help="background cohort for --explain (default: 128 synthetic HF patients; "
+                    help="background cohort for --explain and --explain-pairs (default: 128 synthetic HF patients; "
                          "on --device cpu each background row costs seconds per patient)")
     ap.add_argument("--what-if", nargs="?", const="", default=None, metavar="NAME,NAME",
                     help="risk of the patient as each named variable (default: all) moves over its grid")
@@ -145,7 +174,11 @@ def main(argv=None) -> int:
         p = clf.predict_proba(torch.as_tensor(X, dtype=torch.float64, device=a.device))[:, 1]
         for v in p.cpu().tolist():
             print(f"{v:.6f}")
-        if a.explain:
+        if a.explain_pairs is not None:
+            e = _explainer(a).shap_interaction_values(X)
+            print(format_importance(e.feature_names, e.phi.abs().mean(0).cpu().tolist()))
+            print(format_pair_importance(e, a.explain_pairs))
+        elif a.explain:
             ex = _explainer(a)
             print(format_importance(ex.feature_names, ex.mean_abs(X).cpu().tolist()))
         if a.interactions is not None:
@@ -159,11 +192,14 @@ def main(argv=None) -> int:
             return 2
         params[k] = float(v)
     print(format_probability(predict_patient(params, a.model, a.device)))
-    if a.explain:
+    if a.explain or a.explain_pairs is not None:
         vals = [float(v) for v in params.values()]
-        e = _explainer(a).shap_values([vals])
+        ex = _explainer(a)
+        e = ex.shap_values([vals]) if a.explain_pairs is None else ex.shap_interaction_values([vals])
         print(format_explanation(e.feature_names, vals, e.phi[0].cpu().tolist(), e.base_value,
                                  float(e.prediction[0])))
+        if a.explain_pairs is not None:
+            print(format_pairs(e, a.explain_pairs))
     if a.what_if is not None or a.what_if_csv:
         w = _explainer(a).what_if([[float(v) for v in params.values()]], wi_names)
         if a.what_if is not None:

@@ -5,7 +5,8 @@ question "which variable moved this patient's risk, and by how much" is answered
 interventional Shapley value of each feature against a background cohort.  The stack always
 sees at most 20 columns (17 for the shipped model), so all 2^F coalitions are enumerated
 exactly — no sampling, no KernelSHAP regression — by :func:`hfens.ops.stack_shapley`: one fused
-HIP kernel on ``cuda``, the f64 mirror on the host.
+HIP kernel on ``cuda``, the f64 mirror on the host.  :func:`hfens.ops.stack_shapley_interactions`
+reduces the same coalition table to the Shapley interaction values of every pair as well.
 
 Bit convention: feature k is "present" (takes the patient's value) in coalition S when bit k of
 S is set; absent features take a background row's value.
@@ -63,6 +64,15 @@ class StackExplainer:
     def mean_abs(self, X) -> torch.Tensor:
         """Global importance over a cohort: mean |phi| per feature ([F] f64)."""
         return self.shap_values(X).phi.abs().mean(0)
+
+    def shap_interaction_values(self, X) -> "InteractionExplanation":
+        """Exact Shapley interaction values of each row of ``X`` (:func:`hfens.ops.stack_shapley_interactions`);
+        ``phi``, ``base_value`` and ``prediction`` are :meth:`shap_values`'s, bit for bit."""
+        X = torch.as_tensor(X, dtype=torch.float64)
+        if X.dim() == 1:
+            X = X[None, :]
+        Phi, phi, base, pred = ops.stack_shapley_interactions(X.to(self.device), self.background, self.pk)
+        return InteractionExplanation(Phi, phi, float(base), pred, list(self.feature_names))
 
     # ------------------------------------------------------------------ partial dependence
     def _columns(self, features) -> List[int]:
@@ -190,6 +200,29 @@ def interaction_cells(X: torch.Tensor, pairs, singles):
 def _f32(t: torch.Tensor) -> torch.Tensor:
     """f64 values rounded to f32."""
     return t.to(torch.float32).to(torch.float64)
+
+
+@dataclass
+class InteractionExplanation:
+    Phi: torch.Tensor           # [n, F, F] f64, symmetric: Phi[p, i, j] = half of the pair (i, j)'s effect (SHAP's
+    #                             split); Phi[p, i, i] = the main effect; row i sums to phi[p, i]
+    phi: torch.Tensor           # [n, F] f64 Shapley values
+    base_value: float
+    prediction: torch.Tensor    # [n] f64
+    feature_names: List[str]
+
+    def top(self, n: int, p: int = 0):
+        """The ``n`` strongest pairs of row ``p`` as ``(i, j, 2·Phi[p, i, j])`` with i < j — the full pair
+        effect — by descending magnitude."""
+        F = self.Phi.shape[1]
+        m = self.Phi[p].cpu()
+        pairs = [(i, j, 2.0 * float(m[i, j])) for i in range(F) for j in range(i + 1, F)]
+        return sorted(pairs, key=lambda t: -abs(t[2]))[:n]
+
+    def mean_abs_pairs(self) -> torch.Tensor:
+        """Mean over the rows of |2·Phi[p, i, j]| ([F, F] f64, zero diagonal)."""
+        m = (2.0 * self.Phi).abs().mean(0)
+        return m - torch.diag(torch.diag(m))
 
 
 @dataclass

@@ -8,7 +8,8 @@ from . import reference as ref
 from .packing import pack_forest, pack_stack, pack_svs
 
 __all__ = ["rbf_decision", "svc_proba1", "tree_raw", "expit", "pack_svs", "pack_forest", "pack_stack",
-           "stack_infer", "stack_shapley", "stack_partial", "weighted_moments", "bootstrap_metrics",
+           "stack_infer", "stack_shapley", "stack_shapley_interactions", "shapley_interactions_from_values",
+           "stack_partial", "weighted_moments", "bootstrap_metrics",
            "bootstrap_calibration", "bootstrap_compare"]
 
 
@@ -95,6 +96,9 @@ def stack_infer(x, pk, out=None, grid: int = 0, stream=None):
 
 SHAPLEY_MAX_F = 20                 # v is 8 MB per patient at F = 20
 SHAPLEY_WS_BYTES = 256 << 20       # byte budget of the coalition-value workspace (patients are chunked)
+SHAPLEY_PAIR_GROUP = 16            # pairs (f64 accumulators) per thread of shapley_interactions (csrc/shapley.hip)
+SHAPLEY_PAIR_SLAB = 4096           # coalitions per workgroup there; each of its 256 threads takes 16 of them
+SHAPLEY_PAIR_THREADS = 256
 
 
 def stack_shapley(x, background, pk, *, return_values: bool = False, grid: int = 0, stream=None):
@@ -108,28 +112,34 @@ def stack_shapley(x, background, pk, *, return_values: bool = False, grid: int =
     ``pred [n] = v(all)``, all f64, plus ``v [n, 2^F]`` when ``return_values``; ``phi`` sums to
     ``pred − base`` per row.  ``stream``, if given, is a raw HIP stream handle: the kernels and
     the torch ops that slice the results out all run on it."""
+    return _stack_shapley("stack_shapley", x, background, pk, return_values, grid, stream, False)
+
+
+def _stack_shapley(op: str, x, background, pk, return_values: bool, grid: int, stream, pairs: bool):
+    """``stack_shapley`` (``pairs`` false) and ``stack_shapley_interactions``: validate, then route."""
     if x.dim() != 2 or background.dim() != 2:
-        raise ValueError("stack_shapley: x must be [n, F] and background [B, F]")
+        raise ValueError(f"{op}: x must be [n, F] and background [B, F]")
     n, F = x.shape
     B = background.shape[0]
     if F != pk.F or background.shape[1] != pk.F:
-        raise ValueError(f"stack_shapley: x has {F} and background {background.shape[1]} features, "
+        raise ValueError(f"{op}: x has {F} and background {background.shape[1]} features, "
                          f"model has {pk.F}")
     if F > SHAPLEY_MAX_F:
-        raise ValueError(f"stack_shapley: exact enumeration is limited to {SHAPLEY_MAX_F} features, got {F}")
+        raise ValueError(f"{op}: exact enumeration is limited to {SHAPLEY_MAX_F} features, got {F}")
     if B < 1:
-        raise ValueError("stack_shapley: background needs at least one row")
+        raise ValueError(f"{op}: background needs at least one row")
     if x.device != background.device:
-        raise ValueError("stack_shapley: x and background must be on the same device")
+        raise ValueError(f"{op}: x and background must be on the same device")
     if not x.is_cuda:
-        return ref.stack_shapley(x, background, pk, return_values=return_values)
+        mirror = ref.stack_shapley_interactions if pairs else ref.stack_shapley
+        return mirror(x, background, pk, return_values=return_values)
     if stream is not None:
         with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=x.device)):
-            return _stack_shapley_device(x, background, pk, return_values, grid)
-    return _stack_shapley_device(x, background, pk, return_values, grid)
+            return _stack_shapley_device(x, background, pk, return_values, grid, pairs)
+    return _stack_shapley_device(x, background, pk, return_values, grid, pairs)
 
 
-def _stack_shapley_device(x, background, pk, return_values: bool, grid: int):
+def _stack_shapley_device(x, background, pk, return_values: bool, grid: int, pairs: bool = False):
     """Validated ``cuda`` inputs; everything is enqueued on torch's current stream."""
     from . import ext, stream_ptr
     dev = x.device
@@ -145,6 +155,10 @@ def _stack_shapley_device(x, background, pk, return_values: bool, grid: int):
     per = max(1, SHAPLEY_WS_BYTES // (8 * nS))
     v_all = torch.empty(n, nS, dtype=torch.float64, device=dev) if return_values else None
     ws = None if return_values else torch.empty(min(n, per), nS, dtype=torch.float64, device=dev)
+    if pairs:
+        u = ref.shapley_interaction_weights(F).to(dev)
+        Phi = torch.empty(n, F, F, dtype=torch.float64, device=dev)
+        part = torch.empty(min(n, per) * _pair_part_len(F), dtype=torch.float64, device=dev)
     model = _stack_model_args(pk)
     sp = stream_ptr(dev)
     for p0 in range(0, n, per):
@@ -153,11 +167,63 @@ def _stack_shapley_device(x, background, pk, return_values: bool, grid: int):
         ext().stack_coalition(x32[p0:p1].data_ptr(), p1 - p0, bg32.data_ptr(), B, *model, v.data_ptr(),
                               int(grid), sp)
         ext().shapley_reduce(v.data_ptr(), p1 - p0, F, w.data_ptr(), phi[p0:p1].data_ptr(), sp)
+        if pairs:
+            ext().shapley_interactions(v.data_ptr(), p1 - p0, F, u.data_ptr(), phi[p0:p1].data_ptr(), part.data_ptr(),
+                                       (p1 - p0) * _pair_part_len(F), Phi[p0:p1].data_ptr(), sp)
         pred[p0:p1] = v[:, nS - 1]
         if p0 == 0:
             base = v[0, 0].clone()
-    out = (phi, base, pred)
+    out = (Phi, phi, base, pred) if pairs else (phi, base, pred)
     return out + (v_all,) if return_values else out
+
+
+def _pair_part_len(F: int) -> int:
+    """f64 slab partials ``shapley_interactions`` keeps per patient: slabs × pair groups × group size."""
+    groups = -(-(F * (F - 1) // 2) // SHAPLEY_PAIR_GROUP)
+    return -(-(1 << F) // SHAPLEY_PAIR_SLAB) * groups * SHAPLEY_PAIR_GROUP
+
+
+def stack_shapley_interactions(x, background, pk, *, return_values: bool = False, grid: int = 0, stream=None):
+    """Exact Shapley interaction values of the fused stack's P(class 1), on the coalition values
+    :func:`stack_shapley` is computed from.
+
+    Arguments as :func:`stack_shapley`.  With ``u(s) = s!(F−s−2)!/(2(F−1)!)``, for i ≠ j
+    ``Phi[i][j] = Σ_{S ⊆ N∖{i,j}} u(|S|)·(v(S∪{i,j}) − v(S∪{i}) − v(S∪{j}) + v(S))`` — half of the
+    pair's effect in each of ``[i][j]`` and ``[j][i]``, the SHAP convention — and
+    ``Phi[i][i] = phi[i] − Σ_{j≠i} Phi[i][j]``, so row i sums to ``phi[i]`` and the matrix to
+    ``pred − base``.  Returns ``Phi [n, F, F]`` f64, then ``phi``, ``base``, ``pred`` (and ``v`` with
+    ``return_values``), which are bit-equal to :func:`stack_shapley`'s on the same inputs."""
+    return _stack_shapley("stack_shapley_interactions", x, background, pk, return_values, grid, stream, True)
+
+
+def shapley_interactions_from_values(v, F: int):
+    """Shapley values and interaction values of any game: ``v [n, 2^F]`` f64 (bit k of the column index
+    set: player k present), 1 ≤ F ≤ 20.  Returns ``(Phi [n, F, F], phi [n, F])`` f64 as defined in
+    :func:`stack_shapley_interactions` — ``shapley_reduce`` and ``shapley_interactions`` on ``cuda``,
+    the mirror on the host."""
+    F = int(F)
+    if not 1 <= F <= SHAPLEY_MAX_F:
+        raise ValueError(f"shapley_interactions_from_values: 1 <= F <= {SHAPLEY_MAX_F}, got {F}")
+    if v.dim() != 2 or v.shape[1] != 1 << F:
+        raise ValueError(f"shapley_interactions_from_values: v {tuple(v.shape)} must be [n, {1 << F}]")
+    if v.dtype != torch.float64:
+        raise ValueError("shapley_interactions_from_values: v must be f64")
+    if not v.is_cuda:
+        return ref.shapley_interactions_from_values(v, F)
+    from . import ext, stream_ptr
+    dev = v.device
+    v = v.contiguous()
+    n = v.shape[0]
+    w = ref.shapley_weights(F).to(dev)
+    u = ref.shapley_interaction_weights(F).to(dev)
+    phi = torch.empty(n, F, dtype=torch.float64, device=dev)
+    Phi = torch.empty(n, F, F, dtype=torch.float64, device=dev)
+    part = torch.empty(n * _pair_part_len(F), dtype=torch.float64, device=dev)
+    sp = stream_ptr(dev)
+    ext().shapley_reduce(v.data_ptr(), n, F, w.data_ptr(), phi.data_ptr(), sp)
+    ext().shapley_interactions(v.data_ptr(), n, F, u.data_ptr(), phi.data_ptr(), part.data_ptr(), part.numel(),
+                               Phi.data_ptr(), sp)
+    return Phi, phi
 
 
 PARTIAL_ICE_BYTES = 1 << 30        # largest ice [n, C] f32 that stack_partial returns

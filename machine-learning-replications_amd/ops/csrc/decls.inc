@@ -145,6 +145,8 @@ HFENS_OP(stack_coalition, (uintptr_t X, long long n, uintptr_t BG, long long B, 
                            uintptr_t nodes, uintptr_t values, uintptr_t lr_w, uintptr_t st_off,
                            uintptr_t st_pairs, double st_base, uintptr_t v, int grid, uintptr_t stream))
 HFENS_OP(shapley_reduce, (uintptr_t v, long long n, int F, uintptr_t w, uintptr_t phi, uintptr_t stream))
+HFENS_OP(shapley_interactions, (uintptr_t v, long long n, int F, uintptr_t u, uintptr_t phi, uintptr_t part,
+                                long long part_len, uintptr_t Phi, uintptr_t stream))
 HFENS_OP(stack_partial, (uintptr_t X, long long n, uintptr_t feat, uintptr_t value, long long C, int F, int mp, int T,
                          int K, double ngl2e, double svc_b, double probA, double probB, double gb_init,
                          double gb_lr, double lr_b, double mw0, double mw1, double mw2, double mb,

@@ -3,6 +3,7 @@
 //   h(S,b)[k] = x[k] if bit k of S is set, else bg[b][k]          (hybrid row of coalition S)
 //   v[p][S]   = (1/B)·Σ_b P(h(S,b))                                (stack_coalition, f64)
 //   φ[p][k]   = Σ_S c_k(S)·v[p][S],  c_k(S) = w(|S|−1) if k ∈ S else −w(|S|)   (shapley_reduce, f64)
+//   Φ[p][i][j] = Σ_S c_ij(S)·v[p][S]                                (shapley_interactions, f64; below)
 //
 // stack_coalition evaluates the whole stack on hybrid rows that never exist in HBM; it calls the
 // shared tile body of stack_model.h, which stack_infer calls too, so P is the same function of a
@@ -156,6 +157,156 @@ void shapley_reduce(uintptr_t v, long long n, int F, uintptr_t w, uintptr_t phi,
   if (n == 0) return;
   hipLaunchKernelGGL(shapley_reduce_kernel, dim3((unsigned)n), dim3(256), 0, as_stream(stream),
                      (const double*)v, F, (const double*)w, (double*)phi);
+  launch_check();
+}
+
+// Shapley interaction values from the same table: for i < j
+//   Φ[p][i][j] = Φ[p][j][i] = Σ_T c_ij(T)·v[p][T],
+//   c_ij(T) = u(|T|−2) if both i, j ∈ T, −u(|T|−1) if exactly one is, u(|T|) if neither,
+//   u(s) = s!(F−s−2)!/(2(F−1)!), s ≤ F−2,
+// and Φ[p][i][i] = φ[p][i] − Σ_{j≠i} Φ[p][i][j] (the sum over j ascending, from 0, then one
+// subtraction).  The F(F−1)/2 pairs are numbered row by row — (0,1), (0,2), …, (F−2,F−1) — and
+// split into groups of kPairGroup, the coalitions into slabs of kPairSlab: one workgroup per
+// (patient, group, slab) keeps kPairGroup f64 accumulators per thread, thread t taking
+// coalitions slab·kPairSlab + t, + 256, … in that order.  Per coalition: one popcount, the three
+// products, and per pair popc(bits & pair mask) ∈ {0, 1, 2} selects one of them.  The 256
+// per-thread partials of a pair are folded as 16 runs of 16 consecutive threads, each in thread
+// order, then the 16 runs in run order; shapley_pair_finish folds the slab partials of a pair in
+// slab order, stores both halves and forms the diagonal.  Every order is fixed by the constants
+// alone and there are no atomics, so Φ is bit-identical from run to run.
+constexpr int kPairGroup = 16;      // ops/api.py: SHAPLEY_PAIR_GROUP
+constexpr int kPairSlab = 4096;     // ops/api.py: SHAPLEY_PAIR_SLAB
+constexpr int kPairMax = kShapMaxF * (kShapMaxF - 1) / 2;   // 190 ≤ 256 threads
+
+// pair number q < F(F−1)/2 → (i, j), i < j
+__device__ inline void pair_of(int q, int F, int& i, int& j) {
+  i = 0;
+  for (int len = F - 1; q >= len; --len) {
+    q -= len;
+    ++i;
+  }
+  j = i + 1 + q;
+}
+
+__global__ __launch_bounds__(256) void shapley_pair_partial_kernel(const double* __restrict__ v, int F,
+                                                                   const double* __restrict__ u, int npairs,
+                                                                   int ngroups, int nslab,
+                                                                   double* __restrict__ part) {
+  __shared__ double sh[256][kPairGroup + 1];
+  __shared__ double run[16][kPairGroup + 1];
+  __shared__ double ue[kShapMaxF + 3];   // ue[x] = u(x − 2), 0 outside 0 ≤ x − 2 ≤ F − 2
+  __shared__ unsigned pm[kPairGroup];
+  const int t = threadIdx.x;
+  long long b = blockIdx.x;
+  const int slab = (int)(b % nslab);
+  b /= nslab;
+  const int g = (int)(b % ngroups);
+  const long long p = b / ngroups;
+  const long long nS = 1LL << F;
+  const double* vp = v + (size_t)p * nS;
+  if (t < kShapMaxF + 3) ue[t] = t >= 2 && t <= F ? u[t - 2] : 0.0;
+  if (t < kPairGroup) {
+    const int q = g * kPairGroup + t;
+    unsigned m = 0u;   // a pair past the last one selects u(|T|)·v every time and is never stored
+    if (q < npairs) {
+      int i, j;
+      pair_of(q, F, i, j);
+      m = (1u << i) | (1u << j);
+    }
+    pm[t] = m;
+  }
+  __syncthreads();
+  unsigned mask[kPairGroup];
+#pragma unroll
+  for (int a = 0; a < kPairGroup; ++a) mask[a] = __builtin_amdgcn_readfirstlane(pm[a]);
+  double acc[kPairGroup];
+#pragma unroll
+  for (int a = 0; a < kPairGroup; ++a) acc[a] = 0.0;
+  const long long S0 = (long long)slab * kPairSlab;
+  const long long S1 = S0 + kPairSlab < nS ? S0 + kPairSlab : nS;
+  for (long long S = S0 + t; S < S1; S += 256) {
+    const unsigned bits = (unsigned)S;
+    const int s = __popc(bits);
+    const double vS = vp[S];
+    const double both = ue[s] * vS;          // i, j ∈ T:      u(|T|−2)·v(T)
+    const double one = -(ue[s + 1] * vS);    // one of them:  −u(|T|−1)·v(T)
+    const double none = ue[s + 2] * vS;      // neither:       u(|T|)·v(T)
+#pragma unroll
+    for (int a = 0; a < kPairGroup; ++a) {
+      const int c = __popc(bits & mask[a]);
+      acc[a] += c == 2 ? both : c == 1 ? one : none;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < kPairGroup; ++a) sh[t][a] = acc[a];
+  __syncthreads();
+  {
+    const int a = t & (kPairGroup - 1), r = t >> 4;   // 256 threads = 16 runs × kPairGroup pairs
+    double s = 0.0;
+    for (int k = 0; k < 16; ++k) s += sh[r * 16 + k][a];
+    run[r][a] = s;
+  }
+  __syncthreads();
+  if (t < kPairGroup && g * kPairGroup + t < npairs) {
+    double s = 0.0;
+    for (int r = 0; r < 16; ++r) s += run[r][t];
+    part[((size_t)p * nslab + slab) * ((size_t)ngroups * kPairGroup) + g * kPairGroup + t] = s;
+  }
+}
+
+// One workgroup per patient: thread q folds pair q's slab partials in slab order and stores both
+// halves; then thread i forms the diagonal of row i from the matrix kept in LDS.
+__global__ __launch_bounds__(256) void shapley_pair_finish_kernel(const double* __restrict__ part, int F,
+                                                                  int npairs, int ngroups, int nslab,
+                                                                  const double* __restrict__ phi,
+                                                                  double* __restrict__ Phi) {
+  __shared__ double P[kShapMaxF][kShapMaxF + 1];
+  const int t = threadIdx.x;
+  const size_t p = blockIdx.x;
+  const size_t ld = (size_t)ngroups * kPairGroup;
+  double* out = Phi + p * F * F;
+  if (t < npairs) {
+    int i, j;
+    pair_of(t, F, i, j);
+    const double* q = part + p * nslab * ld + t;
+    double s = 0.0;
+    for (int k = 0; k < nslab; ++k) s += q[(size_t)k * ld];
+    P[i][j] = s;
+    P[j][i] = s;
+    out[i * F + j] = s;
+    out[j * F + i] = s;
+  }
+  __syncthreads();
+  if (t < F) {
+    double s = 0.0;
+    for (int j = 0; j < F; ++j)
+      if (j != t) s += P[t][j];
+    out[t * F + t] = phi[p * F + t] - s;
+  }
+}
+
+void shapley_interactions(uintptr_t v, long long n, int F, uintptr_t u, uintptr_t phi, uintptr_t part,
+                          long long part_len, uintptr_t Phi, uintptr_t stream) {
+  HFENS_REQUIRE(F >= 1 && F <= kShapMaxF, "shapley_interactions: 1 <= F <= 20");
+  static_assert(kPairMax <= 256 && (kPairGroup & (kPairGroup - 1)) == 0 && 256 / kPairGroup == 16,
+                "one finishing thread per pair; 16 runs of 16 threads in the fold");
+  const int npairs = F * (F - 1) / 2;
+  const int ngroups = (npairs + kPairGroup - 1) / kPairGroup;
+  const long long nS = 1LL << F;
+  const int nslab = (int)((nS + kPairSlab - 1) / kPairSlab);
+  HFENS_REQUIRE(n >= 0 && part_len == n * nslab * ngroups * kPairGroup,
+                "shapley_interactions: the partial workspace holds n * slabs * groups * 16 values");
+  if (n == 0) return;
+  const long long blocks = n * ngroups * nslab;
+  HFENS_REQUIRE(blocks <= 0x7fffffffLL && n <= 0x7fffffffLL, "shapley_interactions: too many patients for one call");
+  hipStream_t st = as_stream(stream);
+  if (npairs > 0) {
+    hipLaunchKernelGGL(shapley_pair_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)v, F,
+                       (const double*)u, npairs, ngroups, nslab, (double*)part);
+    launch_check();
+  }
+  hipLaunchKernelGGL(shapley_pair_finish_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)part, F,
+                     npairs, ngroups, nslab, (const double*)phi, (double*)Phi);
   launch_check();
 }
 

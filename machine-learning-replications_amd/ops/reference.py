@@ -216,6 +216,133 @@ def stack_shapley(x: torch.Tensor, background: torch.Tensor, pk, return_values: 
     return out + (v,) if return_values else out
 
 
+# ----------------------------------------------------------------------------- Shapley interactions
+def shapley_interaction_weights(F: int) -> torch.Tensor:
+    """``u(s) = s!(F−s−2)!/(2(F−1)!)`` for s = 0 … F−2 (f64; empty for F = 1): the weight of a
+    coalition of size s that a pair joins, halved so that ``Φ[i][j]`` and ``Φ[j][i]`` each carry half of
+    the pair's effect (the SHAP convention)."""
+    return torch.tensor([math.factorial(s) * math.factorial(F - s - 2) / (2 * math.factorial(F - 1))
+                         for s in range(F - 1)], dtype=torch.float64)
+
+
+def _interaction_coefficients(F: int, s0: int, s1: int):
+    """Coefficients of coalitions s0 ≤ T < s1 (f64).  ``c[T − s0, q]`` for the pairs i < j numbered row by
+    row, q = 0 … F(F−1)/2 − 1: ``u(|T|−2)`` if i and j are both in T, ``−u(|T|−1)`` if exactly one is,
+    ``u(|T|)`` if neither.  ``d[T − s0, i] = c_i(T) − Σ_{j≠i} c_ij(T)``, the diagonal's coefficient, with
+    :func:`shapley_from_values`'s ``c_i`` and the sum in closed form (|T|−1 or |T| partners of i inside T)."""
+    T = torch.arange(s0, s1)
+    inT = ((T[:, None] >> torch.arange(F)[None, :]) & 1)                 # [C, F]
+    size = inT.sum(1)
+    ue = torch.zeros(F + 3, dtype=torch.float64)                         # ue[x] = u(x − 2)
+    ue[2:F + 1] = shapley_interaction_weights(F)
+    table = torch.stack([ue[size + 2], -ue[size + 1], ue[size]], 1)      # by the members of {i, j} in T
+    i, j = torch.triu_indices(F, F, 1)
+    c = table.gather(1, inT[:, i] + inT[:, j])                           # [C, pairs]
+    w = torch.zeros(F + 1, dtype=torch.float64)
+    w[:F] = shapley_weights(F)
+    sz = size.to(torch.float64)[:, None]
+    none, one, both = table[:, 0:1], table[:, 1:2], table[:, 2:3]
+    d = torch.where(inT.bool(), w[(size - 1).clamp(min=0)][:, None] - ((sz - 1) * both + (F - sz) * one),
+                    -w[size][:, None] - (sz * one + (F - 1 - sz) * none))
+    return c, d
+
+
+def _pairs_to_matrix(c: torch.Tensor, F: int) -> torch.Tensor:
+    """``[n, pairs]`` → symmetric ``[n, F, F]`` with a zero diagonal."""
+    i, j = torch.triu_indices(F, F, 1)
+    m = torch.zeros(c.shape[0], F, F, dtype=c.dtype)
+    m[:, i, j] = c
+    m[:, j, i] = c
+    return m
+
+
+def shapley_interaction_abs_sums(F: int, v: torch.Tensor = None, chunk: int = 4096) -> torch.Tensor:
+    """``Σ_T |c_ij(T)|·|v[p, T]|`` as ``[n, F, F]``, or ``Σ_T |c_ij(T)|`` as ``[F, F]`` without ``v``
+    (2 off the diagonal) — what a rounding-error bound of Φ scales with."""
+    nS = 1 << F
+    a = torch.ones(1, nS, dtype=torch.float64) if v is None else v.to(torch.float64).abs()
+    off = torch.zeros(a.shape[0], F * (F - 1) // 2, dtype=torch.float64)
+    diag = torch.zeros(a.shape[0], F, dtype=torch.float64)
+    for s0 in range(0, nS, chunk):
+        s1 = min(nS, s0 + chunk)
+        c, d = _interaction_coefficients(F, s0, s1)
+        off += a[:, s0:s1] @ c.abs()
+        diag += a[:, s0:s1] @ d.abs()
+    out = _pairs_to_matrix(off, F) + torch.diag_embed(diag)
+    return out[0] if v is None else out
+
+
+def shapley_interactions_from_values(v: torch.Tensor, F: int, chunk: int = 4096):
+    """f64 mirror of the ``shapley_interactions`` kernel on any game ``v [n, 2^F]``: off the diagonal
+    ``Φ[p, i, j] = Φ[p, j, i] = Σ_T c_ij(T)·v[p, T]`` (coefficient form, ``chunk`` coalitions at a time),
+    on it ``Φ[p, i, i] = φ[p, i] − Σ_{j≠i} Φ[p, i, j]`` with ``φ`` = :func:`shapley_from_values` and the
+    sum over j ascending from 0.  Returns ``(Phi, phi)``."""
+    v = v.to(torch.float64)
+    n, nS = v.shape[0], 1 << F
+    phi = shapley_from_values(v, F)
+    acc = torch.zeros(n, F * (F - 1) // 2, dtype=torch.float64)
+    for s0 in range(0, nS, chunk):
+        s1 = min(nS, s0 + chunk)
+        acc += v[:, s0:s1] @ _interaction_coefficients(F, s0, s1)[0]
+    Phi = _pairs_to_matrix(acc, F)
+    off = torch.zeros(n, F, dtype=torch.float64)
+    for j in range(F):                                                   # j ascending; Φ[i][i] is 0 here
+        off += Phi[:, :, j]
+    return Phi + torch.diag_embed(phi - off), phi
+
+
+def stack_shapley_interactions(x: torch.Tensor, background: torch.Tensor, pk, return_values: bool = False):
+    """fp64 mirror of ``ops.stack_shapley_interactions``: ``Phi [n, F, F]`` and, exactly as
+    :func:`stack_shapley` returns them, ``phi``, ``base``, ``pred`` and optionally ``v``."""
+    v = coalition_values(x, background, pk)
+    Phi, phi = shapley_interactions_from_values(v, pk.F)
+    out = (Phi, phi, v[0, 0].clone(), v[:, -1].clone())
+    return out + (v,) if return_values else out
+
+
+def shapley_interaction_oracle(v, F: int):
+    """Shapley interaction values straight from the subset-sum definition, numpy ``longdouble``
+    with weights from exact ``Fraction``s; nothing shared with the coefficient form (F ≤ 10).
+
+    ``Φ[i][j] = Σ_{S ⊆ N∖{i,j}} u(|S|)·(v(S∪{i,j}) − v(S∪{i}) − v(S∪{j}) + v(S))`` for i ≠ j,
+    ``φ[i] = Σ_{S ⊆ N∖{i}} w(|S|)·(v(S∪{i}) − v(S))``, ``Φ[i][i] = φ[i] − Σ_{j≠i} Φ[i][j]``.
+    ``v``: [n, 2^F].  Returns ``(Phi [n, F, F], phi [n, F])`` as longdouble arrays."""
+    import numpy as np
+    from fractions import Fraction
+    if not 1 <= F <= 10:
+        raise ValueError("shapley_interaction_oracle: 1 <= F <= 10")
+    L = np.longdouble
+    v = np.asarray(v, dtype=np.float64).astype(L)
+    n = v.shape[0]
+    if v.shape != (n, 1 << F):
+        raise ValueError(f"shapley_interaction_oracle: v must be [n, {1 << F}]")
+    fact = math.factorial
+
+    def ld(fr: Fraction):
+        return L(fr.numerator) / L(fr.denominator)
+
+    w = [ld(Fraction(fact(s) * fact(F - s - 1), fact(F))) for s in range(F)]
+    u = [ld(Fraction(fact(s) * fact(F - s - 2), 2 * fact(F - 1))) for s in range(F - 1)]
+    subsets = np.arange(1 << F)
+    sizes = np.array([bin(int(S)).count("1") for S in subsets])
+    phi = np.zeros((n, F), dtype=L)
+    Phi = np.zeros((n, F, F), dtype=L)
+    for i in range(F):
+        bi = 1 << i
+        S = subsets[(subsets & bi) == 0]
+        wt = np.array([w[s] for s in sizes[S]], dtype=L)
+        phi[:, i] = ((v[:, S | bi] - v[:, S]) * wt).sum(1)
+        for j in range(i + 1, F):
+            bj = 1 << j
+            S2 = S[(S & bj) == 0]
+            ut = np.array([u[s] for s in sizes[S2]], dtype=L)
+            d = v[:, S2 | bi | bj] - v[:, S2 | bi] - v[:, S2 | bj] + v[:, S2]
+            Phi[:, i, j] = Phi[:, j, i] = (d * ut).sum(1)
+    for i in range(F):
+        Phi[:, i, i] = phi[:, i] - Phi[:, i, :].sum(1)        # Φ[i][i] is still 0 in the sum
+    return Phi, phi
+
+
 # ----------------------------------------------------------------------------- partial dependence
 def stack_partial(x: torch.Tensor, pk, feat: torch.Tensor, value: torch.Tensor, return_ice: bool = False,
                   chunk: int = 16384):

@@ -11,6 +11,15 @@ in one process:
 Each path is warmed, then timed ``--reps`` times with device events, alternating the two; the
 median is reported.  A hybrid row is one (patient, coalition, background) evaluation:
 n · 2^F · B of them per call.  Prints one JSON line per shape.
+
+Then the pair reduction (Shapley interaction values) on the table ``v`` that ``stack_coalition`` left
+for the same shape, by the same protocol, as a second JSON line (``"op": "pairs"``):
+
+* fused    — the ``shapley_interactions`` kernels into preallocated buffers;
+* composed — ``v @ C`` in torch with the f64 coefficient matrix ``C [2^F, F²]`` on the same GPU
+  (``composed_s`` is null and ``composed_note`` says why if ``C`` cannot be allocated);
+
+with the whole ``ops.stack_shapley_interactions`` call and ``stack_coalition`` alone beside them.
 """
 from __future__ import annotations
 
@@ -56,6 +65,20 @@ def composed(x, bg, pk, coef, masks):
     return v @ coef, v[0, 0], v[:, -1]
 
 
+def pair_matrix(F, chunk=4096):
+    """``C [2^F, F²]`` f64 with ``(v @ C).reshape(n, F, F)`` = Phi: the mirror's coefficients, the pair
+    columns written to both halves and the diagonal's in place."""
+    i, j = torch.triu_indices(F, F, 1)
+    k = torch.arange(F)
+    C = torch.zeros(1 << F, F * F, dtype=torch.float64)
+    for s0 in range(0, 1 << F, chunk):
+        c, d = ref._interaction_coefficients(F, s0, min(1 << F, s0 + chunk))
+        C[s0:s0 + chunk, i * F + j] = c
+        C[s0:s0 + chunk, j * F + i] = c
+        C[s0:s0 + chunk, k * F + k] = d
+    return C
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--shapes", default="1x256,64x16", help="comma-separated n x B")
@@ -75,6 +98,14 @@ def main(argv=None) -> int:
     zero = torch.zeros((), dtype=torch.float64)
     coef = torch.where(inS, torch.where(size > 0, w[(size - 1).clamp(min=0)], zero)[:, None],
                        -torch.where(size < F, w[size.clamp(max=F - 1)], zero)[:, None]).to(dev)
+
+    u = ref.shapley_interaction_weights(F).to(dev)
+    w_dev = w.to(dev)
+    pair_note = None
+    try:
+        C = pair_matrix(F).to(dev)
+    except torch.OutOfMemoryError as e:
+        C, pair_note = None, f"C [{1 << F}, {F * F}] f64 could not be allocated: {e}"
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -112,7 +143,57 @@ def main(argv=None) -> int:
             "fused_s_min_max": [min(times["fused"]), max(times["fused"])],
             "composed_s_min_max": [min(times["composed"]), max(times["composed"])],
             "max_abs_dphi_between_paths": dphi}), flush=True)
+        pairs_line(n, B, x, bg, pk, u, w_dev, C, pair_note, timed, a)
     return 0
+
+
+def pairs_line(n, B, x, bg, pk, u, w, C, note, timed, a):
+    """Time the pair reduction both ways on the v of this shape and print its JSON line."""
+    from hfens.ops import api
+    dev, F = x.device, pk.F
+    ext, sp = ops.ext(), ops.stream_ptr(dev)
+    phi, _, _, v = ops.stack_shapley(x, bg, pk, return_values=True)
+    Phi = torch.empty(n, F, F, dtype=torch.float64, device=dev)
+    part = torch.empty(n * api._pair_part_len(F), dtype=torch.float64, device=dev)
+    x32, bg32 = x.float().contiguous(), bg.float().contiguous()
+    v2 = torch.empty_like(v)
+    model = api._stack_model_args(pk)
+
+    def fused():
+        ext.shapley_interactions(v.data_ptr(), n, F, u.data_ptr(), phi.data_ptr(), part.data_ptr(), part.numel(),
+                                 Phi.data_ptr(), sp)
+        return Phi
+
+    paths = {"fused": fused,
+             "call": lambda: ops.stack_shapley_interactions(x, bg, pk)[0],
+             "coalition": lambda: ext.stack_coalition(x32.data_ptr(), n, bg32.data_ptr(), B, *model, v2.data_ptr(), 0, sp),
+             "phi_reduce": lambda: ext.shapley_reduce(v.data_ptr(), n, F, w.data_ptr(), phi.data_ptr(), sp)}
+    if C is not None:
+        paths["composed"] = lambda: (v @ C).reshape(n, F, F)
+    for fn in paths.values():
+        for _ in range(a.warmup):
+            fn()
+    torch.cuda.synchronize(dev)
+    times = {k: [] for k in paths}
+    outs = {}
+    for _ in range(a.reps):
+        for k, fn in paths.items():
+            t, outs[k] = timed(fn)
+            times[k].append(t)
+    med = {k: statistics.median(t) for k, t in times.items()}
+    line = {"op": "pairs", "n": n, "B": B, "F": F, "v_bytes": 8 * v.numel()}
+    for k in paths:
+        line[f"{k}_s"] = med[k]
+        line[f"{k}_s_min_max"] = [min(times[k]), max(times[k])]
+    if C is None:
+        line.update(composed_s=None, composed_note=note)
+    else:
+        line["ratio"] = med["composed"] / med["fused"]
+        line["max_abs_dPhi_between_paths"] = float((outs["fused"] - outs["composed"]).abs().max())
+        line["C_bytes"] = 8 * C.numel()
+    line["fused_share_of_call"] = med["fused"] / med["call"]
+    line["call_equals_fused"] = bool(torch.equal(outs["call"], outs["fused"]))
+    print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
