@@ -21,6 +21,13 @@
 //                     (= sklearn's exact splitter on the model's own training rows), Newton leaf
 //                     values Σr/Σh for children of the last level.
 //   gbdt_route      : move rows of split nodes one level down, accumulating child Σw·r².
+//
+// Three paths run these steps: A–D one launch per step (any depth), E the whole boosting of depth-1
+// trees in one workgroup per model, F one launch per stage over row tiles × models.  They agree bit
+// for bit because the arithmetic exists once, in the section "The boosting steps" below: the per-row
+// apply/prepare step, the block sum, the feature classes, the register histogram, the node totals,
+// the best-split search and the split record.  Each kernel keeps only what is its own: where a
+// row's values come from, where sums land, and the layout it stores trees in.
 #include <algorithm>
 #include <cstdlib>
 
@@ -64,173 +71,182 @@ struct GbdtBag {
 };
 
 // ------------------------------------------------------------------------------------------
-// A: apply previous tree (one pending routing level + leaf values) and prepare this stage.
-// prev_* are the previous tree's tables [B][NN] (heap), or nullptr for the first stage.
-__global__ __launch_bounds__(256) void gbdt_apply_prep_kernel(
-    GbdtShape S, const unsigned char* __restrict__ bins, const float* __restrict__ y,
-    const float* __restrict__ w, double* __restrict__ raw, float* __restrict__ g,
-    float* __restrict__ h, int* __restrict__ node, const int* __restrict__ prev_feat,
-    const int* __restrict__ prev_blo, const double* __restrict__ prev_value,
-    long long* __restrict__ prev_r2 /*[B][NN] previous tree Σw r²*/, long long* __restrict__ dev_acc /*[B]*/,
-    long long* __restrict__ cur_r2 /*[B][NN] this tree (root slot)*/, double lr, double qscale,
-    double dscale, GbdtBag bag) {
-  const int b = blockIdx.y;
-  const int lane = threadIdx.x & 63;
-  long long dev_q = 0, r2_q = 0;
-  // per-node Σw r² of the previous tree: block-local LDS accumulation, one global atomic per
-  // (block, node) — a direct global atomic per row serialises on ~3 hot addresses per model
-  __shared__ long long nacc[64];
-  if (threadIdx.x < 64) nacc[threadIdx.x] = 0;
-  __syncthreads();
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < S.n; i += gridDim.x * blockDim.x) {
-    const size_t bi = (size_t)b * S.n + i;
-    const float w0 = w[bi];
-    float wi = w0, wp = w0;   // this stage's / the previous stage's in-bag weight
-    if (bag.active) {
-      const unsigned long long sd = bag.seeds[b];
-      wi = gb_in_bag(sd, bag.stage, bag.row_off + i, bag.thr24) ? w0 : 0.f;
-      wp = (prev_feat != nullptr && gb_in_bag(sd, bag.stage - 1, bag.row_off + i, bag.thr24)) ? w0 : 0.f;
-      bag.wt[bi] = wi;
-    }
-    double rw = raw[bi];
-    const double yi = y[i];
-    if (prev_feat != nullptr) {
-      int nd = node[bi];
-      const int f = prev_feat[b * S.NN + nd];
-      if (f >= 0) {  // pending split at the last level
-        const int side = bins[(size_t)f * S.n + i] <= prev_blo[b * S.NN + nd] ? 1 : 2;
-        nd = 2 * nd + side;
-      }
-      if (wp > 0.f) {
-        const double p0 = 1.0 / (1.0 + exp(-rw));
-        const double r0 = yi - p0;
-        atomicAdd((unsigned long long*)&nacc[nd], (unsigned long long)q_of(wp * r0 * r0, qscale));
-      }
-      rw += lr * prev_value[b * S.NN + nd];
-      raw[bi] = rw;
-    }
-    const double p = 1.0 / (1.0 + exp(-rw));
-    const double r = yi - p;
-    const float gi = (float)(wi * r);
-    const float hi = (float)(wi * p * (1.0 - p));
-    g[bi] = gi;
-    h[bi] = hi;
-    node[bi] = 0;
-    if (wp > 0.f) {
-      // binomial deviance −2(y·raw − log(1+e^raw)) of the previous stage's bag, after its update
-      // (sklearn BinomialDeviance; train_score_ with subsample = in-bag loss)
-      const double l1p = rw > 0 ? rw + log1p(exp(-rw)) : log1p(exp(rw));
-      dev_q += q_of(wp * (-2.0) * (yi * rw - l1p), dscale);
-    }
-    if (wi > 0.f) r2_q += q_of(wi * r * r, qscale);
+// The boosting steps.  Helpers with a __syncthreads() say so: call them under block-uniform control
+// flow only.
+constexpr int kStMaxF = 128;   // features of the depth-1 kernels (E, F)
+
+// Per-row apply/prepare step, in four terms and their composition gb_row_step.
+// This stage's (wi) and the previous stage's (wp) in-bag weight of a row of weight w0.
+__device__ __forceinline__ void gb_row_weights(float w0, bool has_prev, bool has_cur, bool active,
+                                               const unsigned long long* seed, int stage, long long gi,
+                                               unsigned thr24, float& wi, float& wp) {
+  wi = w0; wp = w0;
+  if (active) {
+    const unsigned long long sd = *seed;
+    wi = (has_cur && gb_in_bag(sd, stage, gi, thr24)) ? w0 : 0.f;
+    wp = (has_prev && gb_in_bag(sd, stage - 1, gi, thr24)) ? w0 : 0.f;
   }
-  dev_q = wave_sum_i64(dev_q);
-  r2_q = wave_sum_i64(r2_q);
-  if (lane == 0) {
-    if (prev_feat != nullptr && dev_q != 0) atomicAdd((unsigned long long*)&dev_acc[b], (unsigned long long)dev_q);
-    if (r2_q != 0) atomicAdd((unsigned long long*)&cur_r2[(size_t)b * S.NN], (unsigned long long)r2_q);
-  }
-  __syncthreads();
-  if (prev_feat != nullptr && threadIdx.x < S.NN && nacc[threadIdx.x] != 0)
-    atomicAdd((unsigned long long*)&prev_r2[(size_t)b * S.NN + threadIdx.x],
-              (unsigned long long)nacc[threadIdx.x]);
 }
 
-// ------------------------------------------------------------------------------------------
-// B: histograms.  grid = (row chunks, F, B).  hist layout [B][NL][F][256][3] int64 where the
-// level's nodes are heap indices node0 .. node0+NL-1.
-template <int C>
-__device__ void hist_registers(const unsigned char* __restrict__ col, const float* __restrict__ g,
-                               const float* __restrict__ h, const float* __restrict__ w,
-                               const int* __restrict__ node, int node0, int r0, int r1,
-                               double qscale, long long* __restrict__ out /*[256][3]*/) {
+// The previous tree's leaf Σw·r² term, from raw BEFORE that tree's update.
+__device__ __forceinline__ long long gb_leaf_term(float wp, double rw, double yi, double qscale) {
+  const double p0 = 1.0 / (1.0 + exp(-rw));
+  const double r0 = yi - p0;
+  return q_of(wp * r0 * r0, qscale);
+}
+
+// Binomial deviance −2(y·raw − log(1+e^raw)) of the previous stage's bag, from raw AFTER its update
+// (sklearn BinomialDeviance; train_score_ with subsample = in-bag loss).
+__device__ __forceinline__ long long gb_dev_term(float wp, double rw, double yi, double dscale) {
+  const double l1p = rw > 0 ? rw + log1p(exp(-rw)) : log1p(exp(rw));
+  return q_of(wp * (-2.0) * (yi * rw - l1p), dscale);
+}
+
+// This stage's residual g = w(y−p) and hessian h = w·p(1−p), rounded to f32 as they are summed, and
+// the root Σw·r² term (0 for a row outside the bag).
+__device__ __forceinline__ void gb_row_grad(float wi, double rw, double yi, double qscale, float& g, float& h,
+                                            long long& root_q) {
+  const double p = 1.0 / (1.0 + exp(-rw));
+  const double r = yi - p;
+  g = (float)(wi * r);
+  h = (float)(wi * p * (1.0 - p));
+  root_q = wi > 0.f ? q_of(wi * r * r, qscale) : 0;
+}
+
+// The whole step for the depth-1 kernels: pv is the value of the previous tree's leaf the row falls
+// in.  (The launch path calls the four terms itself, in the order that keeps its registers.)
+struct GbRow {
+  double raw;                       // after the previous tree's update
+  float wi, wp, g, h;
+  long long leaf_q, dev_q, root_q;  // fixed-point terms (0 where the row does not count)
+};
+
+__device__ __forceinline__ GbRow gb_row_step(float w0, double rw, double yi, double pv, bool has_prev,
+                                             bool has_cur, bool active, const unsigned long long* seed,
+                                             int stage, long long gi, unsigned thr24, double lr,
+                                             double qscale, double dscale) {
+  GbRow R;
+  gb_row_weights(w0, has_prev, has_cur, active, seed, stage, gi, thr24, R.wi, R.wp);
+  R.leaf_q = 0; R.dev_q = 0; R.root_q = 0; R.g = 0.f; R.h = 0.f;
+  if (has_prev) {
+    if (R.wp > 0.f) R.leaf_q = gb_leaf_term(R.wp, rw, yi, qscale);
+    rw += lr * pv;
+    if (R.wp > 0.f) R.dev_q = gb_dev_term(R.wp, rw, yi, dscale);
+  }
+  R.raw = rw;
+  if (has_cur) gb_row_grad(R.wi, rw, yi, qscale, R.g, R.h, R.root_q);
+  return R;
+}
+
+// Workgroup sums of NV int64 values (exact) over NW waves: out[0..NV) in LDS, valid for every thread
+// on return.  red is [NW][24].  Two barriers.
+template <int NV, int NW>
+__device__ __forceinline__ void gb_block_sum(long long (&v)[NV], long long* red, long long* out) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const long long s = wave_sum_i64(v[k]);
+    if (lane == 0) red[wave * 24 + k] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < NV) {
+    long long s = 0;
+    for (int k = 0; k < NW; ++k) s += red[k * 24 + threadIdx.x];
+    out[threadIdx.x] = s;
+  }
+  __syncthreads();
+}
+
+// The features of a depth-1 fit by bin count, and the compact histogram layout (feature f's bins
+// start at off[f]).  LDS; thread 0 fills it from nb[0..F) and gets Σ nb back.
+struct GbFeatures {
+  int nb[kStMaxF], off[kStMaxF];
+  int l_bin[kStMaxF], l_one[kStMaxF], l_mid[kStMaxF], l_wide[kStMaxF];   // 2 | ≤ 1 | 3–8 | > 8 bins
+  int n_bin, n_one, n_mid, n_wide;
+};
+
+__device__ __forceinline__ int gb_classify_features(GbFeatures& ft, int F) {
+  int o = 0;
+  ft.n_bin = ft.n_one = ft.n_mid = ft.n_wide = 0;
+  for (int f = 0; f < F; ++f) {
+    const int nb = ft.nb[f];
+    ft.off[f] = o; o += nb;
+    if (nb == 2) ft.l_bin[ft.n_bin++] = f;
+    else if (nb <= 1) ft.l_one[ft.n_one++] = f;
+    else if (nb <= 8) ft.l_mid[ft.n_mid++] = f;
+    else ft.l_wide[ft.n_wide++] = f;
+  }
+  return o;
+}
+
+// Histogram of one ≤ C-bin feature over rows r0 … r1 (those take(i) admits, weight > 0): per-thread
+// registers over the rows, one fold per wave into red[wave][24] as (g, h, w) per bin.  One barrier;
+// the caller adds the waves' entries (gb_red_sum) and lands the sums where its histogram lives.
+template <int C, class Take>
+__device__ __forceinline__ void gb_hist_regs(const unsigned char* __restrict__ col, const float* g,
+                                             const float* h, const float* w, int r0, int r1, int stride,
+                                             double qscale, Take take, long long* red) {
   long long ag[C], ah[C], aw[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) { ag[c] = 0; ah[c] = 0; aw[c] = 0; }
-  for (int i = r0 + threadIdx.x; i < r1; i += blockDim.x) {
-    if (node[i] != node0) continue;
+  for (int i = r0 + threadIdx.x; i < r1; i += stride) {
+    if (!take(i)) continue;
     const float wi = w[i];
     if (!(wi > 0.f)) continue;
     const int bb = col[i];
     const long long qg = q_of(g[i], qscale), qh = q_of(h[i], qscale), qw = q_of(wi, qscale);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const bool m = (bb == c);
+      const bool m = bb == c;
       ag[c] += m ? qg : 0;
       ah[c] += m ? qh : 0;
       aw[c] += m ? qw : 0;
     }
   }
-  __shared__ long long red[4][C * 3];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    long long a = wave_sum_i64(ag[c]), b2 = wave_sum_i64(ah[c]), c2 = wave_sum_i64(aw[c]);
-    if (lane == 0) { red[wave][3 * c] = a; red[wave][3 * c + 1] = b2; red[wave][3 * c + 2] = c2; }
+    const long long a = wave_sum_i64(ag[c]), b2 = wave_sum_i64(ah[c]), c2 = wave_sum_i64(aw[c]);
+    if (lane == 0) {
+      red[wave * 24 + 3 * c] = a;
+      red[wave * 24 + 3 * c + 1] = b2;
+      red[wave * 24 + 3 * c + 2] = c2;
+    }
   }
   __syncthreads();
-  if (threadIdx.x < C * 3) {
-    long long s = 0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k][threadIdx.x];
-    if (s != 0) atomicAdd((unsigned long long*)&out[threadIdx.x], (unsigned long long)s);
-  }
 }
 
-__global__ __launch_bounds__(256) void gbdt_hist_kernel(
-    GbdtShape S, const unsigned char* __restrict__ bins, const int* __restrict__ nbins,
-    const float* __restrict__ g, const float* __restrict__ h, const float* __restrict__ w,
-    const int* __restrict__ node, int node0, int NL, int chunk, long long* __restrict__ hist,
-    double qscale) {
-  const int f = blockIdx.y;
-  const int b = blockIdx.z;
-  const int r0 = blockIdx.x * chunk;
-  const int r1 = min(S.n, r0 + chunk);
-  const size_t boff = (size_t)b * S.n;
-  const unsigned char* col = bins + (size_t)f * S.n;
-  const int nb = nbins[f];
-  long long* hb = hist + (size_t)b * NL * S.F * 768;
-  if (NL == 1) {
-    long long* out = hb + (size_t)f * 768;
-    if (nb <= 2) return hist_registers<2>(col, g + boff, h + boff, w + boff, node + boff, node0, r0, r1, qscale, out);
-    if (nb <= 4) return hist_registers<4>(col, g + boff, h + boff, w + boff, node + boff, node0, r0, r1, qscale, out);
-    if (nb <= 8) return hist_registers<8>(col, g + boff, h + boff, w + boff, node + boff, node0, r0, r1, qscale, out);
-  }
-  // LDS path: NL ≤ 16 nodes × 256 bins × 3 stats × 8 B = up to 96 KiB
-  extern __shared__ __attribute__((aligned(16))) long long lh[];
-  const int tot = NL * nb * 3;
-  for (int k = threadIdx.x; k < tot; k += blockDim.x) lh[k] = 0;
-  __syncthreads();
-  for (int i = r0 + threadIdx.x; i < r1; i += blockDim.x) {
-    const int nd = node[boff + i] - node0;
-    if (nd < 0 || nd >= NL) continue;
-    const float wi = w[boff + i];
-    if (!(wi > 0.f)) continue;
-    const int bb = col[i];
-    long long* cell = lh + ((size_t)nd * nb + bb) * 3;
-    atomicAdd((unsigned long long*)&cell[0], (unsigned long long)q_of(g[boff + i], qscale));
-    atomicAdd((unsigned long long*)&cell[1], (unsigned long long)q_of(h[boff + i], qscale));
-    atomicAdd((unsigned long long*)&cell[2], (unsigned long long)q_of(wi, qscale));
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < tot; k += blockDim.x) {
-    const long long v = lh[k];
-    if (v == 0) continue;
-    const int s = k % 3, bb = (k / 3) % nb, nd = k / (3 * nb);
-    atomicAdd((unsigned long long*)&hb[(((size_t)nd * S.F + f) * 256 + bb) * 3 + s],
-              (unsigned long long)v);
-  }
+template <int NW>
+__device__ __forceinline__ long long gb_red_sum(const long long* red, int k) {
+  long long s = 0;
+  for (int v = 0; v < NW; ++v) s += red[v * 24 + k];
+  return s;
 }
 
-// ------------------------------------------------------------------------------------------
-// C: split finding.  grid = (NL, B), 256 threads (4 waves; wave ↔ features f ≡ wave mod 4).
-struct SplitOut {
-  int* feat;          // [B][NN]  split feature, -2 leaf
-  int* blo;           // [B][NN]  last bin going left
-  double* thr;        // [B][NN]
-  double* value;      // [B][NN]  node value (mean residual for internal, Newton for leaves)
-  long long* stats;   // [B][NN][4] Σw, Σr, Σh, (unused)   (fixed point)
-  const long long* r2;  // [B][NN] Σw r² (filled by apply_prep / route)
+// A node's histograms: feature f's bins [nb[f]][3] = (g, h, w) at h + 3·off[f], or at h + 768·f
+// where off is null (the launch path's [F][256][3]).
+struct GbHist {
+  const long long* h;
+  const int* nb;
+  const int* off;
+  __device__ __forceinline__ const long long* at(int f) const {
+    return h + (off ? (size_t)off[f] * 3 : (size_t)f * 768);
+  }
 };
+
+// Node totals from feature 0's bins, by wave 0: tot = (Σg, Σh, Σw).  One barrier.
+__device__ __forceinline__ void gb_node_totals(GbHist H, long long* tot) {
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x < 64) {
+    const long long* h0 = H.at(0);
+    const int nb0 = H.nb[0];
+    long long a = 0, c = 0, d = 0;
+    for (int bb = lane; bb < nb0; bb += 64) { a += h0[bb * 3]; c += h0[bb * 3 + 1]; d += h0[bb * 3 + 2]; }
+    a = wave_sum_i64(a); c = wave_sum_i64(c); d = wave_sum_i64(d);
+    if (lane == 0) { tot[0] = a; tot[1] = c; tot[2] = d; }
+  }
+  __syncthreads();
+}
 
 __device__ __forceinline__ void scan_feature(const long long* __restrict__ hf, int nb, int lane,
                                              long long tw, long long tg, double min_leaf_q,
@@ -298,6 +314,282 @@ __device__ __forceinline__ void scan_feature_small(const long long* hf, int nb, 
   }
 }
 
+// Best split of a node: friedman_mse proxy (w_r·S_l − w_l·S_r)²/(w_l·w_r) over every cut of every
+// feature.  Wave v scans features order[v], order[v + NW], … (order null: the feature index), then the
+// waves' winners are compared; equal gains go to the lowest rank[f] (rank null: the feature index —
+// lowest feature, lowest bin; then wrk may be wf itself, rank and feature being one number).  Small:
+// features of ≤ 4 bins take scan_feature_small (the stage kernel only).  wg/wf/wbin/wrk are [NW] in
+// LDS.  Two barriers; every thread gets the winner (gain < 0: no admissible cut).
+struct GbBest {
+  double gain;
+  int feat, bin;
+};
+
+template <int NW, bool Small>
+__device__ __forceinline__ GbBest gb_best_split(GbHist H, int F, const int* order, const int* rank,
+                                                long long tw, long long tg, double min_leaf_q,
+                                                double min_split_q, double* wg, int* wf, int* wbin,
+                                                int* wrk) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double bg = -1.0;
+  int bf = 0x7fffffff, bbin = 0, brk = 0x7fffffff;
+  if ((double)tw >= min_split_q) {
+    for (int fo = wave; fo < F; fo += NW) {
+      const int f = order ? order[fo] : fo;
+      const int nb = H.nb[f];
+      double gg;
+      int gb;
+      if (Small && nb <= 4) scan_feature_small(H.at(f), nb, tw, tg, min_leaf_q, gg, gb);
+      else scan_feature(H.at(f), nb, lane, tw, tg, min_leaf_q, gg, gb);
+      const int r = rank ? rank[f] : f;
+      if (gg > bg || (gg == bg && gg >= 0.0 && r < brk)) { bg = gg; bf = f; bbin = gb; brk = r; }
+    }
+  }
+  if (lane == 0) { wg[wave] = bg; wf[wave] = bf; wbin[wave] = bbin; wrk[wave] = brk; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    bg = wg[0]; bf = wf[0]; bbin = wbin[0]; brk = wrk[0];
+    for (int k = 1; k < NW; ++k)
+      if (wg[k] > bg || (wg[k] == bg && wrk[k] < brk)) { bg = wg[k]; bf = wf[k]; bbin = wbin[k]; brk = wrk[k]; }
+    wg[0] = bg; wf[0] = bf; wbin[0] = bbin;
+  }
+  __syncthreads();
+  return GbBest{wg[0], wf[0], wbin[0]};
+}
+
+// impurity == 0 ⇒ leaf (sklearn: impurity <= EPSILON); impurity from the node's Σw·r²
+__device__ __forceinline__ bool gb_can_split(GbBest best, int F, long long tw, long long tg, long long r2,
+                                             double inv) {
+  const double dw = tw * inv, dg = tg * inv;
+  const double imp = r2 * inv / dw - (dg / dw) * (dg / dw);
+  return best.gain >= 0.0 && best.feat < F && imp > 2.220446049250313e-16;
+}
+
+// The chosen bin's left sums (integers: any order), one parallel pass of wave 0 (a serial loop over up
+// to 256 bins by one thread cost more than the rest of the split): out = (Σg, Σh, Σw).  One barrier.
+__device__ __forceinline__ void gb_left_sums(bool can_split, const long long* hf, int bbin, long long* out) {
+  const int lane = threadIdx.x & 63;
+  if (can_split && threadIdx.x < 64) {
+    long long lw = 0, lg = 0, lh = 0;
+    for (int bb = lane; bb <= bbin; bb += 64) { lg += hf[bb * 3]; lh += hf[bb * 3 + 1]; lw += hf[bb * 3 + 2]; }
+    lg = wave_sum_i64(lg);
+    lh = wave_sum_i64(lh);
+    lw = wave_sum_i64(lw);
+    if (lane == 0) { out[0] = lg; out[1] = lh; out[2] = lw; }
+  }
+  __syncthreads();
+}
+
+// Newton leaf value Σr/Σh (sklearn _update_terminal_regions)
+__device__ __forceinline__ double gb_leaf_value(long long sg, long long sh, double inv) {
+  const double den = sh * inv;
+  return fabs(den) < 1e-150 ? 0.0 : sg * inv / den;
+}
+
+// Split record of a node, by one thread: a leaf (feat −2, Newton value) or the split at (feat, blo)
+// with the threshold at the midpoint between the cut bin and the following non-empty bin, the
+// left child's sums and both children's Newton values.  with_thr = false leaves thr unset (workgroups
+// of the stage kernel that store nothing).
+struct GbNode {
+  int feat, blo;
+  double thr, value, vl, vr;
+  long long lw, lg, lh;
+};
+
+__device__ __forceinline__ GbNode gb_split_record(bool can_split, GbBest best, GbHist H, const long long* left,
+                                                  long long tw, long long tg, long long th, double inv,
+                                                  const double* lo_val, const double* hi_val, bool with_thr) {
+  GbNode N{-2, 0, -2.0, 0.0, 0.0, 0.0, 0, 0, 0};
+  if (!can_split) {
+    N.value = gb_leaf_value(tg, th, inv);
+    return N;
+  }
+  const int bf = best.feat, bbin = best.bin;
+  N.feat = bf;
+  N.blo = bbin;
+  N.value = (tg * inv) / (tw * inv);   // internal node value: weighted mean residual
+  N.lg = left[0]; N.lh = left[1]; N.lw = left[2];
+  N.vl = gb_leaf_value(N.lg, N.lh, inv);
+  N.vr = gb_leaf_value(tg - N.lg, th - N.lh, inv);
+  if (with_thr) {
+    const long long* hf = H.at(bf);
+    int hi = bbin + 1;
+    const int nbf = H.nb[bf];
+    while (hi < nbf - 1 && hf[hi * 3 + 2] == 0) ++hi;
+    const double a = hi_val[bf * 256 + bbin], c = lo_val[bf * 256 + hi];
+    double t = a / 2.0 + c / 2.0;
+    if (t == c || isinf(t)) t = a;
+    N.thr = t;
+  }
+  return N;
+}
+
+struct SplitOut {
+  int* feat;          // [..][nodes]  split feature, -2 leaf, -3 unreachable / empty
+  int* blo;           // [..][nodes]  last bin going left
+  double* thr;        // [..][nodes]
+  double* value;      // [..][nodes]  node value (mean residual for internal, Newton for leaves)
+  long long* stats;   // [..][nodes][4] Σw, Σr, Σh, (unused)   (fixed point)
+  const long long* r2;  // [B][NN] Σw r² (filled by apply_prep / route; the launch path only)
+};
+
+// Store a node's record at flat node index i0 and, for a split, its children's sums at iL, iR;
+// leaf_children: the children are leaves and get their Newton values.
+__device__ __forceinline__ void gb_store_node(const SplitOut& o, size_t i0, size_t iL, size_t iR, const GbNode& N,
+                                              long long tw, long long tg, long long th, bool leaf_children) {
+  long long* st = o.stats + i0 * 4;
+  st[0] = tw; st[1] = tg; st[2] = th;
+  o.feat[i0] = N.feat;
+  o.blo[i0] = N.blo;
+  o.thr[i0] = N.thr;
+  o.value[i0] = N.value;
+  if (N.feat < 0) return;
+  long long* sl = o.stats + iL * 4;
+  long long* sr = o.stats + iR * 4;
+  sl[0] = N.lw; sl[1] = N.lg; sl[2] = N.lh;
+  sr[0] = tw - N.lw; sr[1] = tg - N.lg; sr[2] = th - N.lh;
+  if (leaf_children) {
+    o.feat[iL] = -2; o.feat[iR] = -2;
+    o.blo[iL] = 0; o.blo[iR] = 0;
+    o.thr[iL] = -2.0; o.thr[iR] = -2.0;
+    o.value[iL] = N.vl;
+    o.value[iR] = N.vr;
+  }
+}
+
+// The previous stump as the depth-1 kernels' row step reads it (LDS): root feature (−3 empty,
+// −2 leaf), split bin, and the values of the root and its two leaves.
+struct GbPrev {
+  int feat, blo;
+  double v[3];
+};
+
+__device__ __forceinline__ void gb_prev_set(GbPrev& P, int feat, int blo, double v0, double v1, double v2) {
+  P.feat = feat; P.blo = blo; P.v[0] = v0; P.v[1] = v1; P.v[2] = v2;
+}
+
+// ------------------------------------------------------------------------------------------
+// A: apply previous tree (one pending routing level + leaf values) and prepare this stage.
+// prev_* are the previous tree's tables [B][NN] (heap), or nullptr for the first stage.
+__global__ __launch_bounds__(256) void gbdt_apply_prep_kernel(
+    GbdtShape S, const unsigned char* __restrict__ bins, const float* __restrict__ y,
+    const float* __restrict__ w, double* __restrict__ raw, float* __restrict__ g,
+    float* __restrict__ h, int* __restrict__ node, const int* __restrict__ prev_feat,
+    const int* __restrict__ prev_blo, const double* __restrict__ prev_value,
+    long long* __restrict__ prev_r2 /*[B][NN] previous tree Σw r²*/, long long* __restrict__ dev_acc /*[B]*/,
+    long long* __restrict__ cur_r2 /*[B][NN] this tree (root slot)*/, double lr, double qscale,
+    double dscale, GbdtBag bag) {
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const bool has_prev = prev_feat != nullptr;
+  long long dev_q = 0, r2_q = 0;
+  // per-node Σw r² of the previous tree: block-local LDS accumulation, one global atomic per
+  // (block, node) — a direct global atomic per row serialises on ~3 hot addresses per model
+  __shared__ long long nacc[64];
+  if (threadIdx.x < 64) nacc[threadIdx.x] = 0;
+  __syncthreads();
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < S.n; i += gridDim.x * blockDim.x) {
+    const size_t bi = (size_t)b * S.n + i;
+    float wi, wp;
+    gb_row_weights(w[bi], has_prev, true, bag.active, bag.seeds + b, bag.stage, bag.row_off + i, bag.thr24, wi, wp);
+    if (bag.active) bag.wt[bi] = wi;
+    double rw = raw[bi];
+    const double yi = y[i];
+    if (has_prev) {
+      int nd = node[bi];
+      const int f = prev_feat[b * S.NN + nd];
+      if (f >= 0) {  // pending split at the last level
+        const int side = bins[(size_t)f * S.n + i] <= prev_blo[b * S.NN + nd] ? 1 : 2;
+        nd = 2 * nd + side;
+      }
+      if (wp > 0.f) atomicAdd((unsigned long long*)&nacc[nd], (unsigned long long)gb_leaf_term(wp, rw, yi, qscale));
+      rw += lr * prev_value[b * S.NN + nd];
+      raw[bi] = rw;
+    }
+    float gi, hi;
+    long long root_q;
+    gb_row_grad(wi, rw, yi, qscale, gi, hi, root_q);
+    g[bi] = gi;
+    h[bi] = hi;
+    node[bi] = 0;
+    if (wp > 0.f) dev_q += gb_dev_term(wp, rw, yi, dscale);
+    r2_q += root_q;
+  }
+  dev_q = wave_sum_i64(dev_q);
+  r2_q = wave_sum_i64(r2_q);
+  if (lane == 0) {
+    if (prev_feat != nullptr && dev_q != 0) atomicAdd((unsigned long long*)&dev_acc[b], (unsigned long long)dev_q);
+    if (r2_q != 0) atomicAdd((unsigned long long*)&cur_r2[(size_t)b * S.NN], (unsigned long long)r2_q);
+  }
+  __syncthreads();
+  if (prev_feat != nullptr && threadIdx.x < S.NN && nacc[threadIdx.x] != 0)
+    atomicAdd((unsigned long long*)&prev_r2[(size_t)b * S.NN + threadIdx.x],
+              (unsigned long long)nacc[threadIdx.x]);
+}
+
+// ------------------------------------------------------------------------------------------
+// B: histograms.  grid = (row chunks, F, B).  hist layout [B][NL][F][256][3] int64 where the
+// level's nodes are heap indices node0 .. node0+NL-1.
+template <int C>
+__device__ void hist_registers(const unsigned char* __restrict__ col, const float* __restrict__ g,
+                               const float* __restrict__ h, const float* __restrict__ w,
+                               const int* __restrict__ node, int node0, int r0, int r1,
+                               double qscale, long long* __restrict__ out /*[256][3]*/, long long* red) {
+  gb_hist_regs<C>(col, g, h, w, r0, r1, blockDim.x, qscale, [&](int i) { return node[i] == node0; }, red);
+  if (threadIdx.x < C * 3) {
+    const long long s = gb_red_sum<4>(red, threadIdx.x);
+    if (s != 0) atomicAdd((unsigned long long*)&out[threadIdx.x], (unsigned long long)s);
+  }
+}
+
+__global__ __launch_bounds__(256) void gbdt_hist_kernel(
+    GbdtShape S, const unsigned char* __restrict__ bins, const int* __restrict__ nbins,
+    const float* __restrict__ g, const float* __restrict__ h, const float* __restrict__ w,
+    const int* __restrict__ node, int node0, int NL, int chunk, long long* __restrict__ hist,
+    double qscale) {
+  const int f = blockIdx.y;
+  const int b = blockIdx.z;
+  const int r0 = blockIdx.x * chunk;
+  const int r1 = min(S.n, r0 + chunk);
+  const size_t boff = (size_t)b * S.n;
+  const unsigned char* col = bins + (size_t)f * S.n;
+  const int nb = nbins[f];
+  long long* hb = hist + (size_t)b * NL * S.F * 768;
+  if (NL == 1) {
+    __shared__ long long red[4 * 24];
+    long long* out = hb + (size_t)f * 768;
+    if (nb <= 2) return hist_registers<2>(col, g + boff, h + boff, w + boff, node + boff, node0, r0, r1, qscale, out, red);
+    if (nb <= 4) return hist_registers<4>(col, g + boff, h + boff, w + boff, node + boff, node0, r0, r1, qscale, out, red);
+    if (nb <= 8) return hist_registers<8>(col, g + boff, h + boff, w + boff, node + boff, node0, r0, r1, qscale, out, red);
+  }
+  // LDS path: NL ≤ 16 nodes × 256 bins × 3 stats × 8 B = up to 96 KiB
+  extern __shared__ __attribute__((aligned(16))) long long lh[];
+  const int tot = NL * nb * 3;
+  for (int k = threadIdx.x; k < tot; k += blockDim.x) lh[k] = 0;
+  __syncthreads();
+  for (int i = r0 + threadIdx.x; i < r1; i += blockDim.x) {
+    const int nd = node[boff + i] - node0;
+    if (nd < 0 || nd >= NL) continue;
+    const float wi = w[boff + i];
+    if (!(wi > 0.f)) continue;
+    const int bb = col[i];
+    long long* cell = lh + ((size_t)nd * nb + bb) * 3;
+    atomicAdd((unsigned long long*)&cell[0], (unsigned long long)q_of(g[boff + i], qscale));
+    atomicAdd((unsigned long long*)&cell[1], (unsigned long long)q_of(h[boff + i], qscale));
+    atomicAdd((unsigned long long*)&cell[2], (unsigned long long)q_of(wi, qscale));
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < tot; k += blockDim.x) {
+    const long long v = lh[k];
+    if (v == 0) continue;
+    const int s = k % 3, bb = (k / 3) % nb, nd = k / (3 * nb);
+    atomicAdd((unsigned long long*)&hb[(((size_t)nd * S.F + f) * 256 + bb) * 3 + s],
+              (unsigned long long)v);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// C: split finding.  grid = (NL, B), 256 threads (4 waves; wave ↔ features f ≡ wave mod 4).
 __global__ __launch_bounds__(256) void gbdt_split_kernel(
     GbdtShape S, const long long* __restrict__ hist, const int* __restrict__ nbins,
     const double* __restrict__ lo_val, const double* __restrict__ hi_val, int node0, int NL,
@@ -305,85 +597,24 @@ __global__ __launch_bounds__(256) void gbdt_split_kernel(
   const int nd = blockIdx.x;      // node within level
   const int b = blockIdx.y;
   const int hn = node0 + nd;      // heap index
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long* hb = hist + ((size_t)b * NL + nd) * S.F * 768;
-  long long* st = o.stats + ((size_t)b * S.NN + hn) * 4;
-  // node totals from feature 0's bins
+  const GbHist H{hist + ((size_t)b * NL + nd) * S.F * 768, nbins, nullptr};
   __shared__ long long tot[3];
   __shared__ double wg[4];
   __shared__ int wf[4], wbin[4];
-  if (wave == 0) {
-    long long a = 0, c = 0, d = 0;
-    const int nb0 = nbins[0];
-    for (int bb = lane; bb < nb0; bb += 64) { a += hb[bb * 3]; c += hb[bb * 3 + 1]; d += hb[bb * 3 + 2]; }
-    a = wave_sum_i64(a); c = wave_sum_i64(c); d = wave_sum_i64(d);
-    if (lane == 0) { tot[0] = a; tot[1] = c; tot[2] = d; }
-  }
-  __syncthreads();
+  gb_node_totals(H, tot);
   const long long tg = tot[0], th = tot[1], tw = tot[2];
-  if (tw <= 0) {  // unreachable / empty node
-    if (threadIdx.x == 0) { o.feat[b * S.NN + hn] = -3; }
+  const size_t idx = (size_t)b * S.NN + hn;
+  if (tw <= 0) {  // unreachable / empty node (block-uniform)
+    if (threadIdx.x == 0) { o.feat[idx] = -3; }
     return;
   }
-  double bg = -1.0;
-  int bf = 0x7fffffff, bbin = 0;
-  if ((double)tw >= min_split_q) {
-    for (int f = wave; f < S.F; f += 4) {
-      double gg;
-      int gb;
-      scan_feature(hb + (size_t)f * 768, nbins[f], lane, tw, tg, min_leaf_q, gg, gb);
-      if (gg > bg) { bg = gg; bf = f; bbin = gb; }  // f ascending within a wave
-    }
-  }
-  if (lane == 0) { wg[wave] = bg; wf[wave] = bf; wbin[wave] = bbin; }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  bg = wg[0]; bf = wf[0]; bbin = wbin[0];
-  for (int k = 1; k < 4; ++k)
-    if (wg[k] > bg || (wg[k] == bg && wf[k] < bf)) { bg = wg[k]; bf = wf[k]; bbin = wbin[k]; }
-  // node record
-  st[0] = tw; st[1] = tg; st[2] = th;
+  const GbBest best = gb_best_split<4, false>(H, S.F, nullptr, nullptr, tw, tg, min_leaf_q, min_split_q, wg, wf, wbin, wf);
   const double inv = 1.0 / qscale;
-  // impurity==0 ⇒ leaf (sklearn: impurity <= EPSILON); impurity from Σw r² (st[3], filled by prep/route)
-  const double dw = tw * inv, dg = tg * inv;
-  const double imp = o.r2[(size_t)b * S.NN + hn] * inv / dw - (dg / dw) * (dg / dw);
-  const bool can_split = bg >= 0.0 && bf < S.F && imp > 2.220446049250313e-16;
-  const int idx = b * S.NN + hn;
-  if (!can_split) {
-    o.feat[idx] = -2;
-    o.blo[idx] = 0;
-    o.thr[idx] = -2.0;
-    const double den = th * inv;
-    o.value[idx] = fabs(den) < 1e-150 ? 0.0 : dg / den;
-    return;
-  }
-  // children sums at the chosen bin; the following non-empty bin gives the threshold
-  const long long* hf = hb + (size_t)bf * 768;
-  long long lw = 0, lg = 0, lh = 0;
-  for (int bb = 0; bb <= bbin; ++bb) { lg += hf[bb * 3]; lh += hf[bb * 3 + 1]; lw += hf[bb * 3 + 2]; }
-  int hi = bbin + 1;
-  const int nbf = nbins[bf];
-  while (hi < nbf - 1 && hf[hi * 3 + 2] == 0) ++hi;
-  const double a = hi_val[bf * 256 + bbin], c = lo_val[bf * 256 + hi];
-  double t = a / 2.0 + c / 2.0;
-  if (t == c || isinf(t)) t = a;
-  o.feat[idx] = bf;
-  o.blo[idx] = bbin;
-  o.thr[idx] = t;
-  o.value[idx] = dg / dw;  // internal node value: weighted mean residual
-  const int L = 2 * hn + 1, R = 2 * hn + 2;
-  long long* sl = o.stats + ((size_t)b * S.NN + L) * 4;
-  long long* sr = o.stats + ((size_t)b * S.NN + R) * 4;
-  sl[0] = lw; sl[1] = lg; sl[2] = lh;
-  sr[0] = tw - lw; sr[1] = tg - lg; sr[2] = th - lh;
-  if (last_level) {  // children are leaves: Newton values, sklearn _update_terminal_regions
-    o.feat[b * S.NN + L] = -2; o.feat[b * S.NN + R] = -2;
-    o.blo[b * S.NN + L] = 0; o.blo[b * S.NN + R] = 0;
-    o.thr[b * S.NN + L] = -2.0; o.thr[b * S.NN + R] = -2.0;
-    const double dl = lh * inv, dr = (th - lh) * inv;
-    o.value[b * S.NN + L] = fabs(dl) < 1e-150 ? 0.0 : lg * inv / dl;
-    o.value[b * S.NN + R] = fabs(dr) < 1e-150 ? 0.0 : (tg - lg) * inv / dr;
-  }
+  const bool can_split = gb_can_split(best, S.F, tw, tg, o.r2[idx], inv);
+  gb_left_sums(can_split, H.at(can_split ? best.feat : 0), best.bin, tot);
+  if (threadIdx.x != 0) return;
+  const GbNode N = gb_split_record(can_split, best, H, tot, tw, tg, th, inv, lo_val, hi_val, true);
+  gb_store_node(o, idx, (size_t)b * S.NN + 2 * hn + 1, (size_t)b * S.NN + 2 * hn + 2, N, tw, tg, th, last_level != 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -482,16 +713,14 @@ void gbdt_route(int B, int n, int NN, uintptr_t bins, uintptr_t g, uintptr_t w, 
 
 // ------------------------------------------------------------------------------------------
 // E: depth-1 trees on few rows — the whole boosting run in ONE launch (gbdt_stumps_fused).
-//    One 1024-thread workgroup per model runs, for every stage, exactly A (apply_prep) → B (root
-//    histogram) → C (root split) above: same per-row arithmetic, same fixed-point sums, same
-//    split rule and tie-breaks, so trees, leaf values, impurities and train_score_ equal the
-//    launch-per-step path's.  What goes away is 4 launches and the host round trips of every stage
-//    (the bench's 6-model GBC: ≈18 ms of host enqueue for 100 stages).  The root histograms of all
-//    features live in LDS in a compact layout (feature f's bins start at off[f]); ≤ 8-bin features
-//    accumulate in registers and fold once per feature, wider ones use ds_add_u64.
+//    One 1024-thread workgroup per model runs, for every stage, A (apply_prep) → B (root
+//    histogram) → C (root split) with the boosting steps above, so trees, leaf values, impurities
+//    and train_score_ equal the launch-per-step path's.  What goes away is 4 launches and the host
+//    round trips of every stage (the bench's 6-model GBC: ≈18 ms of host enqueue for 100 stages).
+//    The root histograms of all features live in LDS in a compact layout (GbFeatures); ≤ 8-bin
+//    features accumulate in registers and fold once per feature, wider ones use ds_add_u64.
 constexpr int kStThreads = 1024;
 constexpr int kStWaves = kStThreads / 64;
-constexpr int kStMaxF = 128;
 
 struct StumpJob {
   const unsigned char* bins;          // [F][n]
@@ -519,92 +748,23 @@ struct StumpJob {
   int active, B, n, F, T, hist_len;   // hist_len = Σ_f nbins[f]
 };
 
-// Root histogram of one ≤ C-bin feature over the workgroup: per-thread registers, one fold.
-// g/h/w were written by this workgroup earlier in the launch (vector loads, no __restrict__).
-template <int C>
-__device__ __forceinline__ void stump_hist_regs(const unsigned char* __restrict__ col, const float* g,
-                                                const float* h, const float* w, int n, int nb, double qscale,
-                                                long long* out /*[nb][3] LDS*/, long long* red) {
-  long long ag[C], ah[C], aw[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) { ag[c] = 0; ah[c] = 0; aw[c] = 0; }
-  for (int i = threadIdx.x; i < n; i += kStThreads) {
-    const float wi = w[i];
-    if (!(wi > 0.f)) continue;
-    const int bb = col[i];
-    const long long qg = q_of(g[i], qscale), qh = q_of(h[i], qscale), qw = q_of(wi, qscale);
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const bool m = bb == c;
-      ag[c] += m ? qg : 0;
-      ah[c] += m ? qh : 0;
-      aw[c] += m ? qw : 0;
-    }
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const long long a = wave_sum_i64(ag[c]), b2 = wave_sum_i64(ah[c]), c2 = wave_sum_i64(aw[c]);
-    if (lane == 0) {
-      red[wave * 24 + 3 * c] = a;
-      red[wave * 24 + 3 * c + 1] = b2;
-      red[wave * 24 + 3 * c + 2] = c2;
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < 3 * nb) {
-    long long s = 0;
-    for (int k = 0; k < kStWaves; ++k) s += red[k * 24 + threadIdx.x];
-    out[threadIdx.x] = s;
-  }
-  __syncthreads();
-}
-
-// Workgroup sums of NV int64 values (exact): out[0..NV) in LDS, valid for every thread on return.
-template <int NV>
-__device__ __forceinline__ void stump_block_sum(long long (&v)[NV], long long* red, long long* out) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const long long t = wave_sum_i64(v[k]);
-    if (lane == 0) red[wave * 24 + k] = t;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < NV) {
-    long long s = 0;
-    for (int k = 0; k < kStWaves; ++k) s += red[k * 24 + threadIdx.x];
-    out[threadIdx.x] = s;
-  }
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(kStThreads) void gbdt_stumps_fused_kernel(StumpJob J) {
   extern __shared__ __attribute__((aligned(16))) long long hl[];   // [hist_len][3]
   __shared__ long long red[kStWaves * 24];
-  __shared__ int s_nb[kStMaxF], s_off[kStMaxF];
+  __shared__ GbFeatures ft;
   __shared__ long long tot[3], root_r2;
   __shared__ double wg[kStWaves];
   __shared__ int wf[kStWaves], wbin[kStWaves];
-  __shared__ int tf0, tblo, bad;   // previous tree: root feature (−3 empty, −2 leaf) and split bin
-  __shared__ int l_bin[kStMaxF], l_one[kStMaxF], l_mid[kStMaxF], l_wide[kStMaxF];   // features by bin count
-  __shared__ int n_bin, n_one, n_mid, n_wide;
+  __shared__ GbPrev prev;          // previous tree
+  __shared__ int bad;
   __shared__ long long bsum[24];
-  __shared__ double tval[3];       // previous tree: node values
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = J.n, F = J.F, B = J.B;
+  if (tid < F) ft.nb[tid] = J.nbins[tid];
+  __syncthreads();
   if (tid == 0) {
-    int o = 0;
-    n_bin = n_one = n_mid = n_wide = 0;
-    for (int f = 0; f < F; ++f) {
-      const int nb = J.nbins[f];
-      s_nb[f] = nb; s_off[f] = o; o += nb;
-      if (nb == 2) l_bin[n_bin++] = f;
-      else if (nb <= 1) l_one[n_one++] = f;
-      else if (nb <= 8) l_mid[n_mid++] = f;
-      else l_wide[n_wide++] = f;
-    }
-    bad = o != J.hist_len || s_nb[0] < 1;   // host and device bin tables disagree: write nothing
-    tf0 = -3; tblo = 0; tval[0] = tval[1] = tval[2] = 0.0;
+    bad = gb_classify_features(ft, F) != J.hist_len || ft.nb[0] < 1;   // host and device bin tables disagree: write nothing
+    gb_prev_set(prev, -3, 0, 0.0, 0.0, 0.0);
   }
   __syncthreads();
   if (bad) return;
@@ -615,47 +775,31 @@ __global__ __launch_bounds__(kStThreads) void gbdt_stumps_fused_kernel(StumpJob 
   float* h = J.h + boff;
   float* wt = J.active ? J.wt + boff : nullptr;
   const float* wcur = J.active ? wt : wb;
+  const GbHist H{hl, ft.nb, ft.off};
+  const SplitOut o{J.feat, J.blo, J.thr, J.value, J.stats, nullptr};
   for (int t = 0; t <= J.T; ++t) {
-    // ---- A: apply the previous stump, this stage's residuals (gbdt_apply_prep_kernel)
+    // ---- A: apply the previous stump, this stage's residuals
     const bool has_prev = t > 0;
-    const int pf = tf0, pblo = tblo;
-    const double pv0 = tval[0], pv1 = tval[1], pv2 = tval[2];
+    const int pf = prev.feat, pblo = prev.blo;
+    const double pv0 = prev.v[0], pv1 = prev.v[1], pv2 = prev.v[2];
     long long dev_q = 0, r2_q = 0, n0 = 0, n1 = 0, n2 = 0;
     double bag = 0.0;
     for (int i = tid; i < n; i += kStThreads) {
-      const float w0 = wb[i];
-      float wi = w0, wp = w0;
+      const int nd = (has_prev && pf >= 0) ? (J.bins[(size_t)pf * n + i] <= pblo ? 1 : 2) : 0;
+      const GbRow R = gb_row_step(wb[i], raw[i], J.y[i], nd == 0 ? pv0 : (nd == 1 ? pv1 : pv2), has_prev, true,
+                                  J.active, J.seeds + b, t, J.row_off + i, J.thr24, J.lr, J.qscale, J.dscale);
       if (J.active) {
-        const unsigned long long sd = J.seeds[b];
-        wi = gb_in_bag(sd, t, J.row_off + i, J.thr24) ? w0 : 0.f;
-        wp = (has_prev && gb_in_bag(sd, t - 1, J.row_off + i, J.thr24)) ? w0 : 0.f;
-        wt[i] = wi;
-        bag += (double)wi;
+        wt[i] = R.wi;
+        bag += (double)R.wi;
       }
-      double rw = raw[i];
-      const double yi = J.y[i];
-      if (has_prev) {
-        const int nd = pf >= 0 ? (J.bins[(size_t)pf * n + i] <= pblo ? 1 : 2) : 0;
-        if (wp > 0.f) {
-          const double p0 = 1.0 / (1.0 + exp(-rw));
-          const double r0 = yi - p0;
-          const long long q = q_of(wp * r0 * r0, J.qscale);
-          n0 += nd == 0 ? q : 0;
-          n1 += nd == 1 ? q : 0;
-          n2 += nd == 2 ? q : 0;
-        }
-        rw += J.lr * (nd == 0 ? pv0 : (nd == 1 ? pv1 : pv2));
-        raw[i] = rw;
-      }
-      const double p = 1.0 / (1.0 + exp(-rw));
-      const double r = yi - p;
-      g[i] = (float)(wi * r);
-      h[i] = (float)(wi * p * (1.0 - p));
-      if (wp > 0.f) {
-        const double l1p = rw > 0 ? rw + log1p(exp(-rw)) : log1p(exp(rw));
-        dev_q += q_of(wp * (-2.0) * (yi * rw - l1p), J.dscale);
-      }
-      if (wi > 0.f) r2_q += q_of(wi * r * r, J.qscale);
+      if (has_prev) raw[i] = R.raw;
+      n0 += nd == 0 ? R.leaf_q : 0;
+      n1 += nd == 1 ? R.leaf_q : 0;
+      n2 += nd == 2 ? R.leaf_q : 0;
+      g[i] = R.g;
+      h[i] = R.h;
+      dev_q += R.dev_q;
+      r2_q += R.root_q;
     }
     dev_q = wave_sum_i64(dev_q);
     r2_q = wave_sum_i64(r2_q);
@@ -691,10 +835,10 @@ __global__ __launch_bounds__(kStThreads) void gbdt_stumps_fused_kernel(StumpJob 
     }
     __syncthreads();
     if (t == J.T) break;
-    // ---- B: root histograms (gbdt_hist_kernel, NL = 1).  Integer sums are exact, so features
-    // may be grouped freely: node totals once; binary features 8 per row pass (bin 1 summed,
-    // bin 0 = total − bin 1); 3–8-bin features one per pass in registers; every wider feature
-    // in ONE row pass with ds_add_u64.
+    // ---- B: root histograms (NL = 1).  Integer sums are exact, so features may be grouped
+    // freely: node totals once; binary features 8 per row pass (bin 1 summed, bin 0 = total −
+    // bin 1); 3–8-bin features one per pass in registers; every wider feature in ONE row pass
+    // with ds_add_u64.
     for (int k = tid; k < 3 * J.hist_len; k += kStThreads) hl[k] = 0;
     {
       long long v[3] = {0, 0, 0};
@@ -705,10 +849,10 @@ __global__ __launch_bounds__(kStThreads) void gbdt_stumps_fused_kernel(StumpJob 
         v[1] += q_of(h[i], J.qscale);
         v[2] += q_of(wi, J.qscale);
       }
-      stump_block_sum<3>(v, red, tot);
+      gb_block_sum<3, kStWaves>(v, red, tot);
     }
-    for (int b0 = 0; b0 < n_bin; b0 += 8) {
-      const int nf = min(8, n_bin - b0);
+    for (int b0 = 0; b0 < ft.n_bin; b0 += 8) {
+      const int nf = min(8, ft.n_bin - b0);
       long long acc[24];
 #pragma unroll
       for (int k = 0; k < 24; ++k) acc[k] = 0;
@@ -718,37 +862,40 @@ __global__ __launch_bounds__(kStThreads) void gbdt_stumps_fused_kernel(StumpJob 
         const long long qg = q_of(g[i], J.qscale), qh = q_of(h[i], J.qscale), qw = q_of(wi, J.qscale);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-          if (u < nf && J.bins[(size_t)l_bin[b0 + u] * n + i]) {
+          if (u < nf && J.bins[(size_t)ft.l_bin[b0 + u] * n + i]) {
             acc[3 * u] += qg;
             acc[3 * u + 1] += qh;
             acc[3 * u + 2] += qw;
           }
         }
       }
-      stump_block_sum<24>(acc, red, bsum);
+      gb_block_sum<24, kStWaves>(acc, red, bsum);
       if (tid < 3 * nf) {
         const int u = tid / 3, k = tid - 3 * u;
-        const int off = s_off[l_bin[b0 + u]];
+        const int off = ft.off[ft.l_bin[b0 + u]];
         hl[(off + 1) * 3 + k] = bsum[tid];
         hl[off * 3 + k] = tot[k] - bsum[tid];
       }
     }
-    for (int u = tid; u < 3 * n_one; u += kStThreads) hl[s_off[l_one[u / 3]] * 3 + u % 3] = tot[u % 3];
-    for (int u = 0; u < n_mid; ++u) {
-      const int f = l_mid[u], nb = s_nb[f];
+    for (int u = tid; u < 3 * ft.n_one; u += kStThreads) hl[ft.off[ft.l_one[u / 3]] * 3 + u % 3] = tot[u % 3];
+    for (int u = 0; u < ft.n_mid; ++u) {
+      // g/h/w were written by this workgroup earlier in the launch (vector loads, no __restrict__)
+      const int f = ft.l_mid[u], nb = ft.nb[f];
       const unsigned char* col = J.bins + (size_t)f * n;
-      long long* out = hl + (size_t)s_off[f] * 3;
-      if (nb <= 4) stump_hist_regs<4>(col, g, h, wcur, n, nb, J.qscale, out, red);
-      else stump_hist_regs<8>(col, g, h, wcur, n, nb, J.qscale, out, red);
+      const auto all = [](int) { return true; };
+      if (nb <= 4) gb_hist_regs<4>(col, g, h, wcur, 0, n, kStThreads, J.qscale, all, red);
+      else gb_hist_regs<8>(col, g, h, wcur, 0, n, kStThreads, J.qscale, all, red);
+      if (tid < 3 * nb) hl[(size_t)ft.off[f] * 3 + tid] = gb_red_sum<kStWaves>(red, tid);
+      __syncthreads();
     }
-    if (n_wide > 0) {
+    if (ft.n_wide > 0) {
       for (int i = tid; i < n; i += kStThreads) {
         const float wi = wcur[i];
         if (!(wi > 0.f)) continue;
         const long long qg = q_of(g[i], J.qscale), qh = q_of(h[i], J.qscale), qw = q_of(wi, J.qscale);
-        for (int u = 0; u < n_wide; ++u) {
-          const int f = l_wide[u];
-          long long* cell = hl + ((size_t)s_off[f] + J.bins[(size_t)f * n + i]) * 3;
+        for (int u = 0; u < ft.n_wide; ++u) {
+          const int f = ft.l_wide[u];
+          long long* cell = hl + ((size_t)ft.off[f] + J.bins[(size_t)f * n + i]) * 3;
           atomicAdd((unsigned long long*)&cell[0], (unsigned long long)qg);
           atomicAdd((unsigned long long*)&cell[1], (unsigned long long)qh);
           atomicAdd((unsigned long long*)&cell[2], (unsigned long long)qw);
@@ -756,83 +903,24 @@ __global__ __launch_bounds__(kStThreads) void gbdt_stumps_fused_kernel(StumpJob 
       }
     }
     __syncthreads();
-    // ---- C: root split (gbdt_split_kernel's rule; 16 waves scan features f ≡ wave mod 16)
-    if (wave == 0) {
-      long long a = 0, c = 0, d = 0;
-      for (int bb = lane; bb < s_nb[0]; bb += 64) { a += hl[bb * 3]; c += hl[bb * 3 + 1]; d += hl[bb * 3 + 2]; }
-      a = wave_sum_i64(a);
-      c = wave_sum_i64(c);
-      d = wave_sum_i64(d);
-      if (lane == 0) { tot[0] = a; tot[1] = c; tot[2] = d; }
-    }
-    __syncthreads();
+    // ---- C: root split (16 waves scan features f ≡ wave mod 16)
+    gb_node_totals(H, tot);
     const long long tg = tot[0], th = tot[1], tw = tot[2];
     const size_t tb = (size_t)t * B + b;
     if (tw <= 0) {   // empty root (block-uniform)
-      if (tid == 0) { J.feat[tb * 3] = -3; tf0 = -3; tblo = 0; tval[0] = tval[1] = tval[2] = 0.0; }
+      if (tid == 0) { J.feat[tb * 3] = -3; gb_prev_set(prev, -3, 0, 0.0, 0.0, 0.0); }
       __syncthreads();
       continue;
     }
-    double bg = -1.0;
-    int bf = 0x7fffffff, bbin = 0;
-    if ((double)tw >= J.min_split_q) {
-      for (int f = wave; f < F; f += kStWaves) {
-        double gg;
-        int gb;
-        scan_feature(hl + (size_t)s_off[f] * 3, s_nb[f], lane, tw, tg, J.min_leaf_q, gg, gb);
-        if (gg > bg) { bg = gg; bf = f; bbin = gb; }   // f ascending within a wave
-      }
-    }
-    if (lane == 0) { wg[wave] = bg; wf[wave] = bf; wbin[wave] = bbin; }
-    __syncthreads();
+    const GbBest best = gb_best_split<kStWaves, false>(H, F, nullptr, nullptr, tw, tg, J.min_leaf_q, J.min_split_q,
+                                                       wg, wf, wbin, wf);
+    const double inv = 1.0 / J.qscale;
+    const bool can_split = gb_can_split(best, F, tw, tg, root_r2, inv);
+    gb_left_sums(can_split, H.at(can_split ? best.feat : 0), best.bin, tot);
     if (tid == 0) {
-      bg = wg[0]; bf = wf[0]; bbin = wbin[0];
-      for (int k = 1; k < kStWaves; ++k)
-        if (wg[k] > bg || (wg[k] == bg && wf[k] < bf)) { bg = wg[k]; bf = wf[k]; bbin = wbin[k]; }
-      long long* st = J.stats + tb * 3 * 4;
-      st[0] = tw; st[1] = tg; st[2] = th;
-      const double inv = 1.0 / J.qscale;
-      const double dw = tw * inv, dg = tg * inv;
-      const double imp = root_r2 * inv / dw - (dg / dw) * (dg / dw);
-      const bool can_split = bg >= 0.0 && bf < F && imp > 2.220446049250313e-16;
-      tval[1] = 0.0;
-      tval[2] = 0.0;
-      if (!can_split) {
-        J.feat[tb * 3] = -2;
-        J.blo[tb * 3] = 0;
-        J.thr[tb * 3] = -2.0;
-        const double den = th * inv;
-        const double v = fabs(den) < 1e-150 ? 0.0 : dg / den;
-        J.value[tb * 3] = v;
-        tf0 = -2; tblo = 0; tval[0] = v;
-      } else {
-        const long long* hf = hl + (size_t)s_off[bf] * 3;
-        long long lw = 0, lg = 0, lh = 0;
-        for (int bb = 0; bb <= bbin; ++bb) { lg += hf[bb * 3]; lh += hf[bb * 3 + 1]; lw += hf[bb * 3 + 2]; }
-        int hi = bbin + 1;
-        const int nbf = s_nb[bf];
-        while (hi < nbf - 1 && hf[hi * 3 + 2] == 0) ++hi;
-        const double a = J.hi_val[bf * 256 + bbin], c = J.lo_val[bf * 256 + hi];
-        double tt = a / 2.0 + c / 2.0;
-        if (tt == c || isinf(tt)) tt = a;
-        J.feat[tb * 3] = bf;
-        J.blo[tb * 3] = bbin;
-        J.thr[tb * 3] = tt;
-        J.value[tb * 3] = dg / dw;   // internal node value: weighted mean residual
-        long long* sl = st + 4;
-        long long* sr = st + 8;
-        sl[0] = lw; sl[1] = lg; sl[2] = lh;
-        sr[0] = tw - lw; sr[1] = tg - lg; sr[2] = th - lh;
-        J.feat[tb * 3 + 1] = -2; J.feat[tb * 3 + 2] = -2;
-        J.blo[tb * 3 + 1] = 0; J.blo[tb * 3 + 2] = 0;
-        J.thr[tb * 3 + 1] = -2.0; J.thr[tb * 3 + 2] = -2.0;
-        const double dl = lh * inv, dr = (th - lh) * inv;
-        const double vl = fabs(dl) < 1e-150 ? 0.0 : lg * inv / dl;
-        const double vr = fabs(dr) < 1e-150 ? 0.0 : (tg - lg) * inv / dr;
-        J.value[tb * 3 + 1] = vl;
-        J.value[tb * 3 + 2] = vr;
-        tf0 = bf; tblo = bbin; tval[0] = dg / dw; tval[1] = vl; tval[2] = vr;
-      }
+      const GbNode N = gb_split_record(can_split, best, H, tot, tw, tg, th, inv, J.lo_val, J.hi_val, true);
+      gb_store_node(o, tb * 3, tb * 3 + 1, tb * 3 + 2, N, tw, tg, th, true);
+      gb_prev_set(prev, N.feat, N.blo, N.value, N.vl, N.vr);
     }
     __syncthreads();
   }
@@ -879,10 +967,10 @@ void gbdt_stumps_fused(int B, int n, int F, int T, uintptr_t bins, uintptr_t nbi
 // Slots rotate over 3 buffers: launch t reads slot t−1, accumulates slot t and zeroes slot t+1.
 // Between launches the host runs ONE all-reduce of slot t under data parallelism (histogram +
 // extras in one int64 SUM: exact, so every rank computes the identical split) — the whole stage
-// costs one launch and one collective.  Sums, split rule, thresholds and leaf values are the
-// fused kernel's (same fixed-point integers), so trees are bit-identical to it; the only
-// addition is an optional per-tree feature RANK for tie-breaks (sklearn's Fisher–Yates visit
-// order, computed on the host) instead of the lowest feature index.
+// costs one launch and one collective.  Row step, sums, split search and split record are the
+// boosting steps above (same fixed-point integers), so trees are bit-identical to the other
+// paths'; the only addition is an optional per-tree feature RANK for tie-breaks (sklearn's
+// Fisher–Yates visit order, computed on the host) instead of the lowest feature index.
 constexpr int kSgThreads = 512;
 constexpr int kSgWaves = kSgThreads / 64;
 constexpr int kSgTile = 1024;       // rows per workgroup (LDS row cache: 3 × 8 B per row)
@@ -959,63 +1047,6 @@ __device__ __forceinline__ bool sg_grid_barrier(unsigned* bar, unsigned* err, un
   return s_ok != 0;
 }
 
-template <int NV, int NW = kSgWaves>
-__device__ __forceinline__ void sg_block_sum(long long (&v)[NV], long long* red, long long* out) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const long long s = wave_sum_i64(v[k]);
-    if (lane == 0) red[wave * 24 + k] = s;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < NV) {
-    long long s = 0;
-    for (int k = 0; k < NW; ++k) s += red[k * 24 + threadIdx.x];
-    out[threadIdx.x] = s;
-  }
-  __syncthreads();
-}
-
-// ≤ C-bin feature over the tile from the quantised row cache: registers, one fold into LDS.
-template <int C>
-__device__ __forceinline__ void sg_hist_regs(const unsigned char* __restrict__ col, const long long* qg,
-                                             const long long* qh, const long long* qw, int m, int nb,
-                                             long long* out /*[nb][3] LDS*/, long long* red) {
-  long long ag[C], ah[C], aw[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) { ag[c] = 0; ah[c] = 0; aw[c] = 0; }
-  for (int i = threadIdx.x; i < m; i += kSgThreads) {
-    const long long w = qw[i];
-    if (w == 0) continue;
-    const int bb = col[i];
-    const long long g = qg[i], h = qh[i];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const bool k = bb == c;
-      ag[c] += k ? g : 0;
-      ah[c] += k ? h : 0;
-      aw[c] += k ? w : 0;
-    }
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const long long a = wave_sum_i64(ag[c]), b2 = wave_sum_i64(ah[c]), c2 = wave_sum_i64(aw[c]);
-    if (lane == 0) {
-      red[wave * 24 + 3 * c] = a;
-      red[wave * 24 + 3 * c + 1] = b2;
-      red[wave * 24 + 3 * c + 2] = c2;
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < 3 * nb) {
-    long long s = 0;
-    for (int k = 0; k < kSgWaves; ++k) s += red[k * 24 + threadIdx.x];
-    out[threadIdx.x] += s;
-  }
-  __syncthreads();
-}
-
 // MF = true: the histogram of every feature with 2–8 bins (binary features, small ordinals) is an
 // integer GEMM on the matrix cores instead of int64 VALU sums.  The stage's quantised g, h, w
 // (int64 fixed point, |q| < 2^49) are cut into 7 slices of 7 bits (the top slice signed), so
@@ -1066,14 +1097,11 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
   long long* qh = qg + kSgRowPad + kSgArrSkew;
   long long* qw = qh + kSgRowPad + kSgArrSkew;
   __shared__ long long red[kW * 24];
-  __shared__ int s_nb[kStMaxF], s_off[kStMaxF];
-  __shared__ int l_bin[kStMaxF], l_one[kStMaxF], l_mid[kStMaxF], l_wide[kStMaxF];
-  __shared__ int n_bin, n_one, n_mid, n_wide;
-  __shared__ long long tot[3], bsum[24], ext[8];
+  __shared__ GbFeatures ft;
+  __shared__ long long tot[3], ext[8];
   __shared__ double wg[kW];
   __shared__ int wf[kW], wbin[kW], wrk[kW];
-  __shared__ int pf_s, pblo_s;
-  __shared__ double pv_s[3];
+  __shared__ GbPrev prev;          // tree t−1 as the apply reads it
   // MF: indicator rows (feature, bin; −1 = all ones, −2 = padding), MFMA features and their first row
   __shared__ int s_indf[MF ? kSgMaxInd : 1], s_indc[MF ? kSgMaxInd : 1];
   __shared__ int l_mf[MF ? kStMaxF : 1], l_mfi[MF ? kStMaxF : 1];
@@ -1088,46 +1116,37 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
   const size_t slot_sz = (size_t)B * slot_m;
   // the features' bin counts: one load per thread, in parallel (a serial loop of dependent global
   // loads in thread 0 cost several µs per launch)
-  if (tid < F) s_nb[tid] = J.nbins[tid];
+  if (tid < F) ft.nb[tid] = J.nbins[tid];
   __syncthreads();
   if (tid == 0) {
-    int o = 0;
-    n_bin = n_one = n_mid = n_wide = 0;
-    for (int f = 0; f < F; ++f) {
-      const int nb = s_nb[f];
-      s_off[f] = o; o += nb;
-      if (nb == 2) l_bin[n_bin++] = f;
-      else if (nb <= 1) l_one[n_one++] = f;
-      else if (nb <= 8) l_mid[n_mid++] = f;
-      else l_wide[n_wide++] = f;
-    }
+    gb_classify_features(ft, F);
     {
       int o2 = 0;
-      for (int f = 0; f < F; ++f) if (s_nb[f] > 4) s_ord[o2++] = f;
-      for (int f = 0; f < F; ++f) if (s_nb[f] <= 4) s_ord[o2++] = f;
+      for (int f = 0; f < F; ++f) if (ft.nb[f] > 4) s_ord[o2++] = f;
+      for (int f = 0; f < F; ++f) if (ft.nb[f] <= 4) s_ord[o2++] = f;
     }
     if constexpr (MF) {
       int ni = 1;
       s_indf[0] = -1; s_indc[0] = 0;
-      n_mf = 0; n_wide = 0;
+      n_mf = 0; ft.n_wide = 0;
       for (int f = 0; f < F; ++f) {
-        const int nb = s_nb[f];
+        const int nb = ft.nb[f];
         if (nb >= 2 && nb <= 8 && ni + nb - 1 <= kSgMaxInd) {
           l_mf[n_mf] = f; l_mfi[n_mf] = ni; ++n_mf;
           for (int c = 1; c < nb; ++c) { s_indf[ni] = f; s_indc[ni] = c; ++ni; }
         } else if (nb > 1) {
-          l_wide[n_wide++] = f;
+          ft.l_wide[ft.n_wide++] = f;
         }
       }
       n_mb = (ni + 31) / 32;
       for (int i = ni; i < n_mb * 32; ++i) { s_indf[i] = -2; s_indc[i] = 0; }
     }
-    pf_s = -3; pblo_s = 0; pv_s[0] = pv_s[1] = pv_s[2] = 0.0;
+    gb_prev_set(prev, -3, 0, 0.0, 0.0, 0.0);
   }
   for (int t = t_first;; ++t) {
   if constexpr (Persist) {
     if (t > t_first && !sg_grid_barrier(J.bar + b, J.err, (unsigned)(t - t_first) * gridDim.x, J.deadline)) return;
-    if (tid == 0) { pf_s = -3; pblo_s = 0; pv_s[0] = pv_s[1] = pv_s[2] = 0.0; }
+    if (tid == 0) gb_prev_set(prev, -3, 0, 0.0, 0.0, 0.0);
   }
   long long* slot_prev = J.comm + (size_t)((t + 2) % 3) * slot_sz + (size_t)b * slot_m;
   long long* slot_cur = J.comm + (size_t)(t % 3) * slot_sz + (size_t)b * slot_m;
@@ -1215,94 +1234,27 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
       }
     }
     __syncthreads();
-    const long long* hp = hl;
-    if (wave == 0) {
-      long long a = 0, c = 0, d = 0;
-      for (int bb = lane; bb < s_nb[0]; bb += 64) { a += hp[bb * 3]; c += hp[bb * 3 + 1]; d += hp[bb * 3 + 2]; }
-      a = wave_sum_i64(a); c = wave_sum_i64(c); d = wave_sum_i64(d);
-      if (lane == 0) { tot[0] = a; tot[1] = c; tot[2] = d; }
-    }
-    __syncthreads();
+    const GbHist H{hl, ft.nb, ft.off};
+    gb_node_totals(H, tot);
     const long long tg = tot[0], th = tot[1], tw = tot[2];
     const size_t tb = (size_t)(t - 1) * B + b;
-    const int* rk = J.frank ? J.frank + tb * F : nullptr;
-    if (tw <= 0) {
+    if (tw <= 0) {   // empty root (block-uniform)
       if (tid == 0) {
         if (lead) J.feat[tb * 3] = -3;
-        pf_s = -3; pblo_s = 0; pv_s[0] = pv_s[1] = pv_s[2] = 0.0;
+        gb_prev_set(prev, -3, 0, 0.0, 0.0, 0.0);
       }
     } else {
-      double bg = -1.0;
-      int bf = 0x7fffffff, bbin = 0, brk = 0x7fffffff;
-      if ((double)tw >= J.min_split_q) {
-        for (int fo = wave; fo < F; fo += kW) {
-          const int f = s_ord[fo];
-          double gg;
-          int gb;
-          if (s_nb[f] <= 4) scan_feature_small(hp + (size_t)s_off[f] * 3, s_nb[f], tw, tg, J.min_leaf_q, gg, gb);
-          else scan_feature(hp + (size_t)s_off[f] * 3, s_nb[f], lane, tw, tg, J.min_leaf_q, gg, gb);
-          const int r = rk ? rk[f] : f;
-          if (gg > bg || (gg == bg && gg >= 0.0 && r < brk)) { bg = gg; bf = f; bbin = gb; brk = r; }
-        }
-      }
-      if (lane == 0) { wg[wave] = bg; wf[wave] = bf; wbin[wave] = bbin; wrk[wave] = brk; }
-      __syncthreads();
+      const GbBest best = gb_best_split<kW, true>(H, F, s_ord, J.frank ? J.frank + tb * F : nullptr, tw, tg,
+                                                  J.min_leaf_q, J.min_split_q, wg, wf, wbin, wrk);
+      const bool can_split = gb_can_split(best, F, tw, tg, root_r2, inv);
+      gb_left_sums(can_split, H.at(can_split ? best.feat : 0), best.bin, tot);
       if (tid == 0) {
-        bg = wg[0]; bf = wf[0]; bbin = wbin[0]; brk = wrk[0];
-        for (int k = 1; k < kW; ++k)
-          if (wg[k] > bg || (wg[k] == bg && wrk[k] < brk)) { bg = wg[k]; bf = wf[k]; bbin = wbin[k]; brk = wrk[k]; }
-        wg[0] = bg; wf[0] = bf; wbin[0] = bbin;
-      }
-      __syncthreads();
-      bg = wg[0]; bf = wf[0]; bbin = wbin[0];
-      const double dw = tw * inv, dg = tg * inv;
-      const double imp = root_r2 * inv / dw - (dg / dw) * (dg / dw);
-      const bool can_split = bg >= 0.0 && bf < F && imp > 2.220446049250313e-16;
-      if (can_split && wave == 0) {
-        // the chosen bin's left sums: one parallel pass of wave 0 (a serial loop over up to 256
-        // bins × 3 global loads by one thread cost more than the rest of the split)
-        const long long* hf = hp + (size_t)s_off[bf] * 3;
-        long long lw = 0, lg = 0, lh = 0;
-        for (int bb = lane; bb <= bbin; bb += 64) { lg += hf[bb * 3]; lh += hf[bb * 3 + 1]; lw += hf[bb * 3 + 2]; }
-        lg = wave_sum_i64(lg);
-        lh = wave_sum_i64(lh);
-        lw = wave_sum_i64(lw);
-        if (lane == 0) { tot[0] = lg; tot[1] = lh; tot[2] = lw; }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        long long* st = J.stats + tb * 3 * 4;
-        if (lead) { st[0] = tw; st[1] = tg; st[2] = th; }
-        if (!can_split) {
-          const double den = th * inv;
-          const double v = fabs(den) < 1e-150 ? 0.0 : dg / den;
-          if (lead) { J.feat[tb * 3] = -2; J.blo[tb * 3] = 0; J.thr[tb * 3] = -2.0; J.value[tb * 3] = v; }
-          pf_s = -2; pblo_s = 0; pv_s[0] = v; pv_s[1] = 0.0; pv_s[2] = 0.0;
-        } else {
-          const long long* hf = hp + (size_t)s_off[bf] * 3;
-          const long long lg = tot[0], lh = tot[1], lw = tot[2];
-          const double dl = lh * inv, dr = (th - lh) * inv;
-          const double vl = fabs(dl) < 1e-150 ? 0.0 : lg * inv / dl;
-          const double vr = fabs(dr) < 1e-150 ? 0.0 : (tg - lg) * inv / dr;
-          if (lead) {
-            int hi = bbin + 1;
-            const int nbf = s_nb[bf];
-            while (hi < nbf - 1 && hf[hi * 3 + 2] == 0) ++hi;
-            const double a = J.hi_val[bf * 256 + bbin], c = J.lo_val[bf * 256 + hi];
-            double tt = a / 2.0 + c / 2.0;
-            if (tt == c || isinf(tt)) tt = a;
-            J.feat[tb * 3] = bf; J.blo[tb * 3] = bbin; J.thr[tb * 3] = tt; J.value[tb * 3] = dg / dw;
-            long long* sl = st + 4;
-            long long* sr = st + 8;
-            sl[0] = lw; sl[1] = lg; sl[2] = lh;
-            sr[0] = tw - lw; sr[1] = tg - lg; sr[2] = th - lh;
-            J.feat[tb * 3 + 1] = -2; J.feat[tb * 3 + 2] = -2;
-            J.blo[tb * 3 + 1] = 0; J.blo[tb * 3 + 2] = 0;
-            J.thr[tb * 3 + 1] = -2.0; J.thr[tb * 3 + 2] = -2.0;
-            J.value[tb * 3 + 1] = vl; J.value[tb * 3 + 2] = vr;
-          }
-          pf_s = bf; pblo_s = bbin; pv_s[0] = dg / dw; pv_s[1] = vl; pv_s[2] = vr;
-        }
+        // every workgroup of the model needs the tree; only its leader stores it (and looks the
+        // threshold up)
+        const GbNode N = gb_split_record(can_split, best, H, tot, tw, tg, th, inv, J.lo_val, J.hi_val, lead);
+        if (lead) gb_store_node(SplitOut{J.feat, J.blo, J.thr, J.value, J.stats, nullptr}, tb * 3, tb * 3 + 1,
+                                tb * 3 + 2, N, tw, tg, th, true);
+        gb_prev_set(prev, N.feat, N.blo, N.value, N.vl, N.vr);
       }
     }
     __syncthreads();
@@ -1311,8 +1263,8 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
   // ---- 2+3 over this workgroup's rows, 1024 at a time: apply tree t−1, stage t's residuals into
   // the LDS row cache, the stage-t histogram accumulated in LDS across sub-tiles (flushed once)
   const bool has_prev = t >= 1, has_cur = t < T;
-  const int pf = pf_s, pblo = pblo_s;
-  const double pv0 = pv_s[0], pv1 = pv_s[1], pv2 = pv_s[2];
+  const int pf = prev.feat, pblo = prev.blo;
+  const double pv0 = prev.v[0], pv1 = prev.v[1], pv2 = prev.v[2];
   long long acc6[6] = {0, 0, 0, 0, 0, 0};   // dev(t−1), r2 root(t), leaf r2 n0..n2 (t−1), bag(t)
   if (has_cur) {
     for (int k = tid; k < 3 * J.hist_len; k += kT) hl[k] = 0;
@@ -1335,44 +1287,24 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
       if (k >= m) continue;
       const int i = r0 + k;
       const size_t bi = (size_t)b * n + i;
-      const float w0 = w0v[u];
-      float wi = w0, wp = w0;
-      if (J.active) {
-        const unsigned long long sd = J.seeds[b];
-        wi = (has_cur && gb_in_bag(sd, t, J.row_off + i, J.thr24)) ? w0 : 0.f;
-        wp = (has_prev && gb_in_bag(sd, t - 1, J.row_off + i, J.thr24)) ? w0 : 0.f;
-        if (has_cur) J.wt[bi] = wi;
-      }
-      double rw = rwv[u];
-      const double yi = yv[u];
+      const int nd = (has_prev && pf >= 0) ? (bnv[u] <= pblo ? 1 : 2) : 0;
+      const GbRow R = gb_row_step(w0v[u], rwv[u], yv[u], nd == 0 ? pv0 : (nd == 1 ? pv1 : pv2), has_prev, has_cur,
+                                  J.active, J.seeds + b, t, J.row_off + i, J.thr24, J.lr, J.qscale, J.dscale);
+      if (J.active && has_cur) J.wt[bi] = R.wi;
       if (has_prev) {
-        const int nd = pf >= 0 ? (bnv[u] <= pblo ? 1 : 2) : 0;
-        if (wp > 0.f) {
-          const double p0 = 1.0 / (1.0 + exp(-rw));
-          const double r0d = yi - p0;
-          const long long q = q_of(wp * r0d * r0d, J.qscale);
-          acc6[2] += nd == 0 ? q : 0;
-          acc6[3] += nd == 1 ? q : 0;
-          acc6[4] += nd == 2 ? q : 0;
-        }
-        rw += J.lr * (nd == 0 ? pv0 : (nd == 1 ? pv1 : pv2));
-        J.raw[bi] = rw;
-        if (wp > 0.f) {
-          const double l1p = rw > 0 ? rw + log1p(exp(-rw)) : log1p(exp(rw));
-          acc6[0] += q_of(wp * (-2.0) * (yi * rw - l1p), J.dscale);
-        }
+        acc6[2] += nd == 0 ? R.leaf_q : 0;
+        acc6[3] += nd == 1 ? R.leaf_q : 0;
+        acc6[4] += nd == 2 ? R.leaf_q : 0;
+        J.raw[bi] = R.raw;
+        acc6[0] += R.dev_q;
       }
       if (has_cur) {
-        const double p = 1.0 / (1.0 + exp(-rw));
-        const double r = yi - p;
-        const float gf = (float)(wi * r);
-        const float hf = (float)(wi * p * (1.0 - p));
-        const bool in = wi > 0.f;
-        qg[sg_ri(k)] = in ? q_of(gf, J.qscale) : 0;
-        qh[sg_ri(k)] = in ? q_of(hf, J.qscale) : 0;
-        qw[sg_ri(k)] = in ? q_of(wi, J.qscale) : 0;
-        if (in) acc6[1] += q_of(wi * r * r, J.qscale);
-        if (J.active) acc6[5] += in ? q_of(wi, J.qscale) : 0;
+        const bool in = R.wi > 0.f;
+        qg[sg_ri(k)] = in ? q_of(R.g, J.qscale) : 0;
+        qh[sg_ri(k)] = in ? q_of(R.h, J.qscale) : 0;
+        qw[sg_ri(k)] = in ? q_of(R.wi, J.qscale) : 0;
+        acc6[1] += R.root_q;
+        if (J.active) acc6[5] += in ? q_of(R.wi, J.qscale) : 0;
       }
     }
     if (r0 + kSgTile < w1r) {
@@ -1463,8 +1395,8 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
           wq2[j] = qw[ri]; gq2[j] = qg[ri]; hq2[j] = qh[ri];
         }
         const unsigned char* bt = J.bins + r0 + kb;
-        for (int fi = 0; fi < n_wide; ++fi) {
-          const int f = l_wide[fi], off = s_off[f];
+        for (int fi = 0; fi < ft.n_wide; ++fi) {
+          const int f = ft.l_wide[fi], off = ft.off[f];
           const unsigned char* bf_ = bt + (size_t)f * J.ldb;
           unsigned v2;
           if constexpr (RL == 4) v2 = *reinterpret_cast<const unsigned*>(bf_);
@@ -1512,7 +1444,7 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
         for (int u = 0; u < 4; ++u) {
         const int f = fg + u * kW;
         if (f >= F) break;
-        const int nb = s_nb[f], off = s_off[f];
+        const int nb = ft.nb[f], off = ft.off[f];
         const uint4 v4 = pre[u];
         const unsigned wd[4] = {v4.x, v4.y, v4.z, v4.w};
         if (nb <= 1) {
@@ -1588,11 +1520,11 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
       // slice sums → int64 bins: bin c ≥ 1 of an MFMA feature is its indicator row, bin 0 the node
       // total (all-ones row) minus the others; constant features get the total
       __syncthreads();
-      for (int u = tid; u < 3 * (n_mf + n_one); u += kT) {
+      for (int u = tid; u < 3 * (n_mf + ft.n_one); u += kT) {
         const int fi = u / 3, v = u - 3 * fi;
         const long long tot_v = sg_comb(Tsl, 0, v);
         if (fi < n_mf) {
-          const int f = l_mf[fi], i0 = l_mfi[fi], off = s_off[f], nb = s_nb[f];
+          const int f = l_mf[fi], i0 = l_mfi[fi], off = ft.off[f], nb = ft.nb[f];
           long long rest = 0;
           for (int cb = 1; cb < nb; ++cb) {
             const long long sv = sg_comb(Tsl, i0 + cb - 1, v);
@@ -1601,13 +1533,13 @@ __global__ __launch_bounds__(NT) void gbdt_stump_stage_kernel(StageJob J) {
           }
           hl[off * 3 + v] += tot_v - rest;
         } else {
-          hl[s_off[l_one[fi - n_mf]] * 3 + v] += tot_v;
+          hl[ft.off[ft.l_one[fi - n_mf]] * 3 + v] += tot_v;
         }
       }
     }
   }
   if (pst && tid == 0) pst[2] = (long long)__builtin_amdgcn_s_memtime() - t_0;
-  sg_block_sum<6, kW>(acc6, red, ext);
+  gb_block_sum<6, kW>(acc6, red, ext);
   // publish: int64 atomics straight into the slot (the default at every grid size: measured faster
   // than the partial slots + reduce launch up to 245 workgroups per model, sg_plan), or plain stores
   // of the whole partial slot for gbdt_stage_reduce_kernel (HFENS_SG_ATOMIC_GROUPS)

@@ -138,3 +138,88 @@ def test_stump_paths_certified(dev, monkeypatch, F, path, ties):
     s = fit_stumps(F, dev, ties)
     assert hist_gbdt.LAST_PATH["path"] == path
     assert_stump_cases(s, check_stumps(s))
+
+
+# ---- the edges of the boosting steps that the three depth-1 paths share (ops/csrc/gbdt.hip) ----
+EDGE_ROWS = 2100          # two full 1,024-row sub-tiles and one of 52 rows
+EDGE_DISTINCT = (1, 2, 3, 4, 5, 8, 9, 64, 256)
+EDGE_ATTRS = ("tree_feature_", "tree_threshold_", "tree_value_", "tree_impurity_",
+              "tree_weighted_n_node_samples_", "train_score_")
+# variant -> (STUMP_PATH, HFENS_GBDT_MFMA, HFENS_SG_THREADS, HFENS_SG_ATOMIC_GROUPS, PERSIST)
+EDGE_VARIANTS = {
+    "launch": ("launch", None, None, None, "0"),
+    "fused": ("fused", None, None, None, "0"),
+    "stage_valu": ("stage", "0", "512", None, "0"),
+    "stage_mfma": ("stage", "1", "512", None, "0"),
+    "stage_mfma_1024": ("stage", "1", "1024", None, "0"),
+    "stage_partials": ("stage", "1", "512", "1", "0"),
+    "stage_persist_valu": ("stage", "0", "512", None, "1"),
+    "stage_persist_mfma": ("stage", "1", "512", None, "1"),
+}
+_EDGE_DATA = []
+
+
+def _edge_data():
+    """Nine columns with 1, 2, 3, 4, 5, 8, 9, 64 and 256 distinct values (every value present: the last has
+    bin 4*63 + 3), labels that depend on three of them, and four row masks: all rows, every third row out,
+    only rows below 1,024 (two sub-tiles of zero weights), and 420 rows (below min_samples_split = 500)."""
+    if not _EDGE_DATA:
+        n = EDGE_ROWS
+        g = torch.Generator().manual_seed(77)
+        cols = [(torch.arange(n) % k)[torch.randperm(n, generator=g)].double() * 0.5 for k in EDGE_DISTINCT]
+        X = torch.stack(cols, 1).contiguous()
+        z = 0.9 * (X[:, 1] - 0.25) + 0.4 * (X[:, 4] - 1.0) + (X[:, 8] - 64.0) / 32.0
+        y = (torch.rand(n, generator=g, dtype=torch.float64) < torch.sigmoid(z)).double()
+        masks = torch.ones(4, n, dtype=torch.bool)
+        masks[1, ::3] = False
+        masks[2, 1024:] = False
+        masks[3] = False
+        masks[3, ::5] = True
+        _EDGE_DATA.append((X, y, masks))
+    return _EDGE_DATA[0]
+
+
+def _edge_fit(dev, monkeypatch, variant, subsample):
+    from hfens.models import hist_gbdt
+    from hfens.models.gbdt import GradientBoostingClassifier
+    path, mf, nt, atomic, persist = EDGE_VARIANTS[variant]
+    monkeypatch.setattr(hist_gbdt, "STUMP_PATH", path)
+    monkeypatch.setattr(hist_gbdt, "FUSED_STUMPS", path == "fused")
+    monkeypatch.setattr(hist_gbdt, "PERSIST", persist)
+    for name, val in (("HFENS_GBDT_MFMA", mf), ("HFENS_SG_THREADS", nt), ("HFENS_SG_ATOMIC_GROUPS", atomic)):
+        if val is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, val)
+    X, y, masks = _edge_data()
+    ms = [GradientBoostingClassifier(n_estimators=4, max_depth=1, subsample=subsample, min_samples_split=500,
+                                     random_state=s) for s in (2020, 7, 8, 9)]
+    hist_gbdt.fit_gbdt_batch(ms, X.to(dev), y.to(dev), masks.to(dev))
+    assert hist_gbdt.LAST_PATH["path"] == path
+    if path == "stage":
+        assert hist_gbdt.GRAPH_INFO["persist"] == (persist == "1")
+    return ms
+
+
+@pytest.mark.parametrize("ties", [False, True])
+@pytest.mark.parametrize("subsample", [1.0, 0.7])
+def test_stump_paths_equal_at_step_edges(dev, monkeypatch, subsample, ties):
+    """Four stages of four stump models on 2,100 rows (sub-tiles of 1,024, 1,024 and 52 rows) and nine
+    columns whose bin counts sit on both sides of every threshold of the shared steps — constant, binary,
+    3, 4 | 5 (small-feature scan), 8 | 9 (register / matrix-core histogram against LDS atomics), 64 and 256
+    (the last lane's last bin) — with one model whose last two sub-tiles carry no weight and one whose root
+    stays below min_samples_split in every stage.  Every path and every stage-kernel instantiation (VALU
+    and MFMA at 512 threads, MFMA at 1,024, partial slots with the reduce launch, both persistent loops)
+    gives the launch path's trees bit for bit; with sklearn's tie ranks on, which the launch and fused
+    paths ignore, the stage variants agree among themselves."""
+    from hfens.models import hist_gbdt
+    monkeypatch.setattr(hist_gbdt, "SKLEARN_TIES", ties)
+    names = [v for v in EDGE_VARIANTS if not ties or EDGE_VARIANTS[v][0] == "stage"]
+    out = {v: _edge_fit(dev, monkeypatch, v, subsample) for v in names}
+    base = out[names[0]]
+    assert all(int(t) == -2 for t in base[3].tree_feature_[:, 0]), "model 3's roots must stay leaves"
+    assert any(int(t) >= 0 for t in base[0].tree_feature_[:, 0]), "model 0 must split"
+    for v in names[1:]:
+        for a, b in zip(base, out[v]):
+            for attr in EDGE_ATTRS:
+                assert torch.equal(getattr(a, attr), getattr(b, attr)), (v, attr)
