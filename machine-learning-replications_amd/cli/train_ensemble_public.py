@@ -16,7 +16,9 @@ and thresholded rates from N bootstrap resamples, and a bootstrap band on the RO
 slope, ECE and net benefit of the held-out risks, a reliability and a decision-curve figure;
 intervals from the same resamples with ``--bootstrap N``), ``--compare`` (is the stack better than each of
 its base learners: paired ΔAUROC, ΔAP, NRI and IDI on the same resamples, DeLong's test and one ROC
-figure of all four models; points and DeLong only with ``--bootstrap 0``); under ``torchrun`` the development rows are sharded
+figure of all four models; points and DeLong only with ``--bootstrap 0``), ``--importance [R]`` (permutation
+importance of the selected variables on the held-out rows: the fall of AUROC and AP and the rise of the
+Brier score over R shuffles, ``--importance-seed``, and a bar figure); under ``torchrun`` the development rows are sharded
 over ranks.
 """
 from __future__ import annotations
@@ -59,9 +61,16 @@ def main(argv=None, script_dir=None) -> int:
                          "their confidence intervals and p-values from the same resamples")
     ap.add_argument("--calibration-bins", type=int, default=10)
     ap.add_argument("--calibration-thresholds", type=int, default=99)
+    ap.add_argument("--importance", type=int, nargs="?", const=30, default=0, metavar="R",
+                    help="permutation importance of the selected variables on the held-out rows: R shuffles "
+                         "(30 when given without a value), the same ones for every variable; the fall of AUROC "
+                         "and AP and the rise of the Brier score (default 0 = off)")
+    ap.add_argument("--importance-seed", type=int, default=2020)
     a = ap.parse_args(argv)
     if a.bootstrap < 0:
         ap.error("--bootstrap must be >= 0")
+    if a.importance < 0:
+        ap.error("--importance must be >= 0")
     if a.no_plots:
         a.plots = None
 
@@ -101,7 +110,15 @@ def main(argv=None, script_dir=None) -> int:
     # are drawn from it, six times, in the stacking fit's order
     np.random.seed(cfg.seed)
     res = develop(X_dev, y_dev, X_sel, y_sel, names, device=device, group=group, cfg=cfg,
-                  **({"keep_bases": True} if a.compare else {}))
+                  **({"keep_bases": True} if a.compare else {}),
+                  **({"keep_heldout": True} if a.importance else {}))
+    if a.importance:
+        # what the stack itself sees: the imputed, selected held-out columns (gathered on EVERY rank)
+        X_imp = res.X_sel
+        y_imp = torch.as_tensor(y_sel, device=X_imp.device)
+        if group is not None:
+            X_imp = pdist.all_gather_rows(X_imp, group)
+            y_imp = pdist.all_gather_rows(y_imp.to(X_imp.dtype)[:, None], group)[:, 0]
     if a.plots or a.bootstrap or a.calibration or a.compare:
         # collectives on EVERY rank (before the rank-0 block); only rank 0 draws
         p_all = res.proba_sel
@@ -168,8 +185,32 @@ def main(argv=None, script_dir=None) -> int:
                 c = comp["comparisons"][name]
                 print(f"stack vs {name}: ΔAUROC {diff(c['delta_auroc'], c['delong'])}   ΔAP {diff(c['delta_ap'])}"
                       f"   NRI {diff(c['nri'])}   IDI {diff(c['idi'])}")
+        imp = None
+        if a.importance:
+            from .. import ops
+            from ..explain import PermutationImportance
+            pk = res.model._packed_stack(X_imp.device)
+            if pk is None:
+                ap.error("--importance needs the HF-shaped stack (scaler+SVC, GBC, LR -> LR)")
+            pi = PermutationImportance(list(res.selected_names), *ops.permutation_importance(
+                X_imp, y_imp, pk, a.importance, seed=a.importance_seed))
+            lo, hi = (v.cpu().tolist() for v in pi.interval("auroc", 0.95))
+            sd = pi.std("auroc").cpu().tolist()
+            m_ap, m_br = pi.mean("ap").cpu().tolist(), pi.mean("brier").cpu().tolist()
+            print(f"permutation importance ({a.importance} shuffles of {X_imp.shape[0]} held-out rows; baseline "
+                  f"AUROC {pi.baseline['auroc']:.4f}   AP {pi.baseline['ap']:.4f}   Brier {pi.baseline['brier']:.4f})")
+            width = max(len(nm) for nm in pi.names)
+            rows = []
+            for k, name, m in pi.top(len(pi.names)):
+                print(f"  {name:<{width}s}  ΔAUROC {m:+.4f} ± {sd[k]:.4f} (95% {lo[k]:+.4f}–{hi[k]:+.4f})"
+                      f"   ΔAP {m_ap[k]:+.4f}   ΔBrier {m_br[k]:+.4f}")
+                rows.append({"name": name, "auroc": {"mean": m, "sd": sd[k], "lo": lo[k], "hi": hi[k]},
+                             "ap": m_ap[k], "brier": m_br[k]})
+            imp = {"n_repeats": a.importance, "seed": a.importance_seed, "baseline": pi.baseline, "variables": rows}
         if a.timings:
             print(res.timer.table())
+        if a.plots and imp is not None:
+            print("importance plot:", metrics.save_importance_plot(imp, a.plots))
         if a.plots:
             band = (ci["fpr_grid"], ci["tpr_lo"], ci["tpr_hi"]) if ci else None
             print("plots:", metrics.save_plots(y_all, p_all, a.plots, band=band))
@@ -193,6 +234,8 @@ def main(argv=None, script_dir=None) -> int:
                     line["calibration"] = cal
                 if comp is not None:
                     line["compare"] = comp
+                if imp is not None:
+                    line["importance"] = imp
                 f.write(json.dumps(line) + "\n")
     pdist.shutdown()
     return 0

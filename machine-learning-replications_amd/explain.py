@@ -14,7 +14,7 @@ S is set; absent features take a background row's value.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import torch
 
@@ -175,6 +175,17 @@ class StackExplainer:
         return Interactions(h2, n, list(self.feature_names))
 
 
+    # ------------------------------------------------------------------ permutation importance
+    def permutation_importance(self, X, y, n_repeats: int = 30, seed: int = 2020) -> "PermutationImportance":
+        """Permutation importance of every column on the held-out rows ``X [n, F]`` with labels ``y [n]``
+        (:func:`hfens.ops.permutation_importance`): how far AUROC and AP fall, and the Brier score rises,
+        when the column is shuffled — ``n_repeats`` shuffles, the same ones for every column."""
+        X = torch.as_tensor(X, dtype=torch.float64).to(self.device)
+        y = torch.as_tensor(y).to(self.device)
+        base, imp = ops.permutation_importance(X, y, self.pk, n_repeats, seed=seed)
+        return PermutationImportance(list(self.feature_names), base, imp)
+
+
 def interaction_cells(X: torch.Tensor, pairs, singles):
     """The cells Friedman's H² needs over cohort ``X`` ([n, F], f32-representable): for every pair
     (j, k) and row i the two-variable cell ``(j, x_ij, k, x_ik)``, then for every single k and row i
@@ -242,6 +253,37 @@ class WhatIf:
     cohort: List[torch.Tensor]   # per variable [G] f64: PD of the background cohort on the same grid
     prediction: torch.Tensor     # [m] f64 P(class 1) of each patient as entered
     x: torch.Tensor              # [m, F] f64 the patients, rounded to f32
+
+
+@dataclass
+class PermutationImportance:
+    names: List[str]
+    baseline: Dict[str, float]            # auroc, ap, brier of the rows as they are
+    importances: Dict[str, torch.Tensor]  # metric → [F, R] f64; positive: the variable helps (auroc, ap: the
+    #                                       fall under permutation; brier: the rise)
+
+    def mean(self, metric: str = "auroc") -> torch.Tensor:
+        return self.importances[metric].mean(1)
+
+    def std(self, metric: str = "auroc") -> torch.Tensor:
+        """Sample standard deviation over the repeats (ddof = 1; NaN with one repeat)."""
+        v = self.importances[metric]
+        if v.shape[1] < 2:
+            return torch.full((v.shape[0],), float("nan"), dtype=v.dtype, device=v.device)
+        return v.std(1, unbiased=True)
+
+    def interval(self, metric: str = "auroc", level: float = 0.95):
+        """Percentile interval over the repeats: ``(lo [F], hi [F])``."""
+        a = (1.0 - level) / 2.0
+        q = torch.tensor([a, 1.0 - a], dtype=torch.float64, device=self.importances[metric].device)
+        lo, hi = torch.quantile(self.importances[metric], q, dim=1)
+        return lo, hi
+
+    def top(self, n: int, metric: str = "auroc"):
+        """The ``n`` most important variables as ``(k, name, mean importance)``, descending (ties: by column)."""
+        m = self.mean(metric).cpu().tolist()
+        order = sorted(range(len(m)), key=lambda k: (-m[k], k))
+        return [(k, self.names[k], m[k]) for k in order[:n]]
 
 
 @dataclass

@@ -10,7 +10,8 @@ from .packing import pack_forest, pack_stack, pack_svs
 __all__ = ["rbf_decision", "svc_proba1", "tree_raw", "expit", "pack_svs", "pack_forest", "pack_stack",
            "stack_infer", "stack_shapley", "stack_shapley_interactions", "shapley_interactions_from_values",
            "stack_partial", "weighted_moments", "bootstrap_metrics",
-           "bootstrap_calibration", "bootstrap_compare"]
+           "bootstrap_calibration", "bootstrap_compare", "permutation_sources", "stack_permute_scores",
+           "rank_metrics", "permutation_importance"]
 
 
 def _c(t: torch.Tensor, dtype) -> torch.Tensor:
@@ -508,6 +509,232 @@ def _compare_device(y, scores, *, seed, stratified, threshold, b0, b1, grid):
                             b0, B, int(use_lds), ws.data_ptr() if ws is not None else 0, slices,
                             *(t.data_ptr() for t in out), int(grid), stream_ptr(dev))
     return out
+
+
+PERMUTE_MAX_N = BOOTSTRAP_MAX_N    # row index i < 2^25 shares the counter with the repeat
+PERMUTE_MAX_R = BOOTSTRAP_MAX_B    # repeat index r < 2^24
+PERMUTE_MAX_F = 64                 # stack_infer's limit
+PERMUTE_WS_BYTES = 256 << 20       # byte budget of the score workspace S (score rows (k, r) are chunked)
+PERMUTE_LDS_ROWS = 12500           # rows whose 13 B (u32 key, two u32 cumulative counts, u8 label) fit the CU's 160 KiB LDS beside 544 B of scratch (csrc/permute.hip)
+_PERMUTE_FORCE_GLOBAL = False      # tests: take the presorted global path below the LDS limit too
+
+
+def permutation_sources(n: int, r0: int, r1: int, seed: int = 0, device="cpu"):
+    """``src [r1 − r0, n]`` (int32): row r is the permutation of repeat ``r0 + r`` under the law of
+    ``reference.permutation_sources`` — the stable ascending argsort of counter-based keys, int64 torch
+    ops on either device, so the tensor is the same on ``cpu`` and ``cuda`` and repeat r does not depend
+    on the range it is computed in."""
+    n, r0, r1 = int(n), int(r0), int(r1)
+    if not 1 <= n <= PERMUTE_MAX_N:
+        raise ValueError(f"permutation_sources: n = {n} outside 1..{PERMUTE_MAX_N}")
+    if not 0 <= r0 <= r1 <= PERMUTE_MAX_R:
+        raise ValueError(f"permutation_sources: r0:r1 = {r0}:{r1} is not a range within 0..{PERMUTE_MAX_R}")
+    return ref.permutation_sources(n, r0, r1, seed, device)
+
+
+def _permute_x_args(op: str, x, pk):
+    if x.dim() != 2:
+        raise ValueError(f"{op}: x {tuple(x.shape)} must be [n, F]")
+    n, F = x.shape
+    if F != pk.F:
+        raise ValueError(f"{op}: x has {F} features, model has {pk.F}")
+    if F > PERMUTE_MAX_F:
+        raise ValueError(f"{op}: the fused stack is limited to {PERMUTE_MAX_F} features, got {F}")
+    if n == 0:
+        raise ValueError(f"{op}: x is empty (n = 0)")
+    if n > PERMUTE_MAX_N:
+        raise ValueError(f"{op}: x has {n} rows, the limit is n <= {PERMUTE_MAX_N}")
+    if x.device != pk.mean.device:
+        raise ValueError(f"{op}: x and the packed model must be on the same device")
+    if not x.is_floating_point() or not bool(torch.isfinite(x.to(torch.float32)).all()):
+        raise ValueError(f"{op}: x must be finite floating point")
+
+
+def stack_permute_scores(x, pk, src, features, *, grid: int = 0, stream=None):
+    """Scores of the permuted cohort: ``S [K, R, n]`` with ``S[kf, r, i]`` = P(class 1) of ``x[i]`` with
+    column ``k = features[kf]`` replaced by ``x[src[r, i], k]`` (``k = −1``: the row as it is).
+
+    ``x``: [n, F] f32 or f64 on ``pk``'s device (rounded to f32 as ``stack_infer`` does); ``src``: [R, n]
+    integer with values in [0, n) on the same device; ``features``: a sequence or 1-D integer tensor of
+    columns in [−1, F).  Returns f32 on ``cuda`` (one fused kernel; the hybrid rows never reach HBM and
+    ``S`` is bit-identical for every ``grid``), the f64 mirror on the host.  ``K·R·n`` must stay below 2^31:
+    :func:`permutation_importance` chunks.  ``stream``, if given, is a raw HIP stream handle."""
+    op = "stack_permute_scores"
+    _permute_x_args(op, x, pk)
+    n, F = x.shape
+    if src.dim() != 2 or src.shape[1] != n or src.shape[0] < 1:
+        raise ValueError(f"{op}: src {tuple(src.shape)} must be [R, {n}] with R >= 1")
+    if src.is_floating_point() or src.dtype == torch.bool:
+        raise ValueError(f"{op}: src must be integer")
+    if src.device != x.device:
+        raise ValueError(f"{op}: x and src must be on the same device")
+    if bool(((src < 0) | (src >= n)).any()):
+        raise ValueError(f"{op}: src must hold row indices in [0, {n})")
+    feat = torch.as_tensor(features, dtype=torch.int64).reshape(-1).cpu()
+    K, R = feat.numel(), src.shape[0]
+    if K < 1 or bool(((feat < -1) | (feat >= F)).any()):
+        raise ValueError(f"{op}: features must be a non-empty list of columns in [-1, {F})")
+    if K * R * n >= 1 << 31:
+        raise ValueError(f"{op}: K*R*n = {K * R * n} must stay below 2^31")
+    if not x.is_cuda:
+        return ref.stack_permute_scores(x, pk, src, feat)
+    return _on_stream(stream, x.device, _permute_scores_device, x, pk, src, feat, grid)
+
+
+def _permute_scores_device(x, pk, src, feat, grid: int, xt=None):
+    """Validated ``cuda`` inputs; everything is enqueued on torch's current stream."""
+    from . import ext, stream_ptr
+    dev = x.device
+    n, F = x.shape
+    x32 = _c(x, torch.float32)
+    if xt is None:
+        xt = x32.t().contiguous()       # column-major copy: the gathered value is one 4-byte read
+    s32 = _c(src, torch.int32)
+    k32 = feat.to(device=dev, dtype=torch.int32).contiguous()
+    K, R = k32.numel(), s32.shape[0]
+    S = torch.empty(K, R, n, dtype=torch.float32, device=dev)
+    ext().stack_permute(x32.data_ptr(), xt.data_ptr(), n, s32.data_ptr(), R, k32.data_ptr(), K,
+                        *_stack_model_args(pk), S.data_ptr(), int(grid), stream_ptr(dev))
+    return S
+
+
+def _labels_args(op: str, y, n: int, device):
+    if y.dim() != 1 or y.numel() != n:
+        raise ValueError(f"{op}: y {tuple(y.shape)} must be [n] with n = {n}")
+    if y.device != device:
+        raise ValueError(f"{op}: y must be on the device of the rows it labels")
+    if not bool(((y == 0) | (y == 1)).all()):
+        raise ValueError(f"{op}: y must hold labels 0 and 1 only")
+    P = int((y == 1).sum())
+    if P == 0 or P == n:
+        raise ValueError(f"{op}: both classes must be present in y")
+
+
+def rank_metrics(y, scores, *, grid: int = 0, stream=None):
+    """Rank every row of ``scores [M, n]`` (f32 or f64) against the binary labels ``y [n]`` on one
+    device: M models or M score vectors in one launch.  Returns a :class:`reference.RankMetrics` (a tuple
+    with named fields): ``a2 [M]`` (int64), the exact doubled AUROC numerator over tie groups, ``auroc`` =
+    ``a2 / (2·P·N)``, ``ap`` (average precision, ties grouped) and ``brier`` = ``Σ(score − y)² / n`` (f64).
+    On ``cuda`` the scores are rounded to f32 and each row is sorted inside the kernel up to
+    ``PERMUTE_LDS_ROWS`` rows; above that ``torch.sort`` orders them and the same kernel runs on its
+    presorted path.  ``a2`` and ``auroc`` do not depend on the path.  ``stream``: a raw HIP stream handle."""
+    op = "rank_metrics"
+    if scores.dim() != 2 or y.dim() != 1 or scores.shape[1] != y.numel():
+        raise ValueError(f"{op}: y {tuple(y.shape)} must be [n] and scores {tuple(scores.shape)} [M, n] of one length n")
+    n = y.numel()
+    if n == 0:
+        raise ValueError(f"{op}: y and scores are empty (n = 0)")
+    if n > PERMUTE_MAX_N:
+        raise ValueError(f"{op}: y has {n} rows, the limit is n <= {PERMUTE_MAX_N}")
+    if not scores.is_floating_point() or not bool(torch.isfinite(scores).all()):
+        raise ValueError(f"{op}: scores must be finite floating point")
+    _labels_args(op, y, n, scores.device)
+    if not scores.is_cuda:
+        return ref.rank_metrics(y, scores)
+    return _on_stream(stream, scores.device, _rank_device, y, scores, grid)
+
+
+def _rank_device(y, scores, grid: int):
+    """Validated ``cuda`` inputs; everything is enqueued on torch's current stream."""
+    from . import ext, stream_ptr
+    dev = scores.device
+    S = _c(scores, torch.float32)
+    M, n = S.shape
+    y8 = (y > 0).to(torch.uint8).contiguous()
+    f64 = torch.float64
+    out = ref.RankMetrics(torch.empty(M, dtype=torch.int64, device=dev), torch.empty(M, dtype=f64, device=dev),
+                          torch.empty(M, dtype=f64, device=dev), torch.empty(M, dtype=f64, device=dev))
+    sp = stream_ptr(dev)
+    if n <= PERMUTE_LDS_ROWS and not _PERMUTE_FORCE_GLOBAL:
+        ext().rank_rows(S.data_ptr(), y8.data_ptr(), 0, 0, n, M, 1, 0, 0, *(t.data_ptr() for t in out),
+                        int(grid), sp)
+        return out
+    # presorted path.  The arrays this function keeps stay within BOOTSTRAP_WS_BYTES: at most half of it
+    # for the scan arrays (8n B per resident workgroup; 8n <= 2^28 B), the rest for the presorted rows of a
+    # chunk (13n B per score row: 4 B sorted score + 8 B sort index + 1 B label; 13n < 2^29 B).
+    # torch.sort's own temporaries come on top of that
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    slices = max(1, min(M, 2 * ncu, (BOOTSTRAP_WS_BYTES // 2) // (8 * n)))
+    ws = torch.empty(slices, 2 * n, dtype=torch.int32, device=dev)
+    per = max(1, (BOOTSTRAP_WS_BYTES - 8 * n * slices) // (13 * n))
+    for c0 in range(0, M, per):
+        c1 = min(M, c0 + per)
+        ss, order = torch.sort(S[c0:c1], dim=1, descending=True)
+        ys = y8[order].contiguous()
+        ext().rank_rows(S[c0:c1].data_ptr(), y8.data_ptr(), ss.data_ptr(), ys.data_ptr(), n, c1 - c0, 0,
+                        ws.data_ptr(), slices, *(t[c0:c1].data_ptr() for t in out), int(grid), sp)
+    return out
+
+
+def permutation_importance(x, y, pk, n_repeats: int, *, seed: int = 0, features=None, r0: int = 0, r1=None,
+                           grid: int = 0, stream=None):
+    """Permutation importance of the fused stack on the held-out rows ``x [n, F]`` with labels ``y [n]``.
+
+    Repeat r permutes the rows by ``permutation_sources`` (one permutation per repeat, shared by every
+    column: a paired design); column k of repeat r is scored on ``x`` with column k taken from the
+    permuted rows, and every score row is ranked against ``y`` (:func:`stack_permute_scores`,
+    :func:`rank_metrics`: two fused kernels on ``cuda``, the f64 mirrors on the host).  The baseline is
+    the unpermuted cohort through the same two ops.  Returns ``(baseline, importances)``: ``baseline`` =
+    ``{"auroc", "ap", "brier"}`` (floats) and ``importances[metric]`` = ``[F', R]`` f64 for the columns
+    ``features`` (default all) and repeats ``r0:r1`` (default all ``n_repeats``): ``baseline − permuted``
+    for ``auroc`` and ``ap``, ``permuted − baseline`` for ``brier`` — positive means the variable helps.
+    Score rows are chunked so that ``S`` stays under ``PERMUTE_WS_BYTES``; no result depends on the
+    chunking, the range or ``grid``.  ``stream``, if given, is a raw HIP stream handle."""
+    op = "permutation_importance"
+    _permute_x_args(op, x, pk)
+    n, F = x.shape
+    _labels_args(op, y, n, x.device)
+    n_repeats = int(n_repeats)
+    if not 1 <= n_repeats <= PERMUTE_MAX_R:
+        raise ValueError(f"{op}: n_repeats = {n_repeats} outside 1..{PERMUTE_MAX_R}")
+    r1 = n_repeats if r1 is None else int(r1)
+    r0 = int(r0)
+    if not 0 <= r0 <= r1 <= n_repeats:
+        raise ValueError(f"{op}: r0:r1 = {r0}:{r1} is not a range within 0..n_repeats = {n_repeats}")
+    cols = list(range(F)) if features is None else [int(k) for k in features]
+    if not cols or any(not 0 <= k < F for k in cols):
+        raise ValueError(f"{op}: features must be a non-empty list of columns in [0, {F})")
+    return _on_stream(stream if x.is_cuda else None, x.device, _permutation_importance, x, y, pk, cols, seed,
+                      r0, r1, grid)
+
+
+def _permutation_importance(x, y, pk, cols, seed, r0, r1, grid):
+    dev = x.device
+    n = x.shape[0]
+    K, R = len(cols), r1 - r0
+    if x.is_cuda:
+        x = _c(x, torch.float32)
+        xt = x.t().contiguous()
+
+        def score(src, feat):
+            return _permute_scores_device(x, pk, src, torch.as_tensor(feat), grid, xt=xt)
+
+        def rank(S):
+            return _rank_device(y, S.reshape(-1, n), grid)
+    else:
+        def score(src, feat):
+            return ref.stack_permute_scores(x, pk, src, torch.as_tensor(feat))
+
+        def rank(S):
+            return ref.rank_metrics(y, S.reshape(-1, n))
+    ident = torch.arange(n, dtype=torch.int32, device=dev)[None, :]
+    b = rank(score(ident, [-1]))
+    base = {"auroc": b.auroc[0], "ap": b.ap[0], "brier": b.brier[0]}
+    perm = {m: torch.empty(K, R, dtype=torch.float64, device=dev) for m in base}
+    rows = max(1, PERMUTE_WS_BYTES // (4 * n))        # score rows (k, r) per chunk of S
+    rc = min(R, rows)                                 # repeats per chunk, then columns per chunk
+    kc = max(1, rows // rc) if rc == R else 1
+    for c0 in range(0, R, rc):
+        c1 = min(R, c0 + rc)
+        src = ref.permutation_sources(n, r0 + c0, r0 + c1, seed, dev)
+        for k0 in range(0, K, kc):
+            k1 = min(K, k0 + kc)
+            m = rank(score(src, cols[k0:k1]))
+            for name in perm:
+                perm[name][k0:k1, c0:c1] = getattr(m, name).reshape(k1 - k0, c1 - c0)
+    imp = {"auroc": base["auroc"] - perm["auroc"], "ap": base["ap"] - perm["ap"],
+           "brier": perm["brier"] - base["brier"]}
+    return {k: float(v) for k, v in base.items()}, imp
 
 
 def expit(x):

@@ -154,6 +154,16 @@ HFENS_OP(stack_partial, (uintptr_t X, long long n, uintptr_t feat, uintptr_t val
                          uintptr_t nodes, uintptr_t values, uintptr_t lr_w, uintptr_t st_off,
                          uintptr_t st_pairs, double st_base, uintptr_t pd, uintptr_t ice, int grid,
                          uintptr_t stream))
+HFENS_OP(stack_permute, (uintptr_t X, uintptr_t Xt, long long n, uintptr_t src, long long R, uintptr_t feat,
+                         long long K, int F, int mp, int T, int Kn, double ngl2e, double svc_b, double probA,
+                         double probB, double gb_init, double gb_lr, double lr_b, double mw0, double mw1,
+                         double mw2, double mb, uintptr_t mean, uintptr_t inv_scale, uintptr_t svt, uintptr_t sn,
+                         uintptr_t coef, uintptr_t nodes, uintptr_t values, uintptr_t lr_w, uintptr_t st_off,
+                         uintptr_t st_pairs, double st_base, uintptr_t S, int grid, uintptr_t stream))
+HFENS_OP(rank_lds_rows, (uintptr_t out))
+HFENS_OP(rank_rows, (uintptr_t S, uintptr_t y, uintptr_t ss, uintptr_t ys, long long n, long long M, int use_lds,
+                     uintptr_t ws, long long ws_slices, uintptr_t a2, uintptr_t auroc, uintptr_t ap,
+                     uintptr_t brier, int grid, uintptr_t stream))
 HFENS_OP(ws_init, (uintptr_t probs, int P, int max_l, uintptr_t zcat, int F, uintptr_t zn, uintptr_t alpha,
                    uintptr_t G, uintptr_t states, uintptr_t keys, long long n, uintptr_t hist, uintptr_t gkey,
                    uintptr_t stream))

@@ -91,16 +91,19 @@ __device__ __forceinline__ void boot_scan(unsigned* cp, unsigned* cn, const unsi
 // Rank statistics of one scanned score order: the tie-group sums for the doubled AUROC numerator
 // (u64, exact) and AP (f64: chunk → wave xor tree → waves in order, which depends on n alone), then
 // thread 0 writes a2, pn (unless null), auroc, ap and the confusion counts of the first k0 rows.
-// Group k ends at row e = glast[e] and starts at f = gfirst[e].  Pb, Nb = cp[n−1], cn[n−1].
-__device__ __forceinline__ void boot_rank_stats(const unsigned* cp, const unsigned* cn, const int* gfirst,
-                                                const int* glast, const BootThread& t, unsigned Pb, unsigned Nb,
+// The tie groups come from the caller: group(e, f), called on the thread's rows in row order, says
+// whether row e ends its group and, if it does, sets f to the group's first row.
+// Pb, Nb = cp[n−1], cn[n−1].
+template <class Group>
+__device__ __forceinline__ void boot_rank_stats(const unsigned* cp, const unsigned* cn, Group group,
+                                                const BootThread& t, unsigned Pb, unsigned Nb,
                                                 int k0, unsigned long long* sc_a2, double* sc_ap, long long* a2_out,
                                                 long long* pn, double* auroc, double* ap, long long* conf) {
   unsigned long long a2 = 0;
   double apv = 0.0;
   for (int e = t.r0; e < t.r1; ++e) {
-    if (glast[e] != e) continue;
-    const int f = gfirst[e];
+    int f;
+    if (!group(e, f)) continue;
     const unsigned tp = cp[e], fp = cn[e];
     const unsigned tp0 = f > 0 ? cp[f - 1] : 0u, fp0 = f > 0 ? cn[f - 1] : 0u;
     a2 += (unsigned long long)(fp - fp0) * (unsigned long long)(tp + tp0);
@@ -126,6 +129,18 @@ __device__ __forceinline__ void boot_rank_stats(const unsigned* cp, const unsign
     conf[2] = Pb - tp;
     conf[3] = Nb - fp;
   }
+}
+
+// The same with the tie groups precomputed: group k ends at row e = glast[e] and starts at f = gfirst[e].
+__device__ __forceinline__ void boot_rank_stats(const unsigned* cp, const unsigned* cn, const int* gfirst,
+                                                const int* glast, const BootThread& t, unsigned Pb, unsigned Nb,
+                                                int k0, unsigned long long* sc_a2, double* sc_ap, long long* a2_out,
+                                                long long* pn, double* auroc, double* ap, long long* conf) {
+  boot_rank_stats(cp, cn, [gfirst, glast](int e, int& f) {
+    if (glast[e] != e) return false;
+    f = gfirst[e];
+    return true;
+  }, t, Pb, Nb, k0, sc_a2, sc_ap, a2_out, pn, auroc, ap, conf);
 }
 
 // The launch path of the three ops: the requirements they share, the grid, the LDS-or-global launch.

@@ -1383,6 +1383,100 @@ def bootstrap_compare(y: torch.Tensor, scores: torch.Tensor, n_boot: int, *, see
     return CompareBootstrap(*(torch.cat(o) for o in outs))
 
 
+# ---- permutation importance -----------------------------------------------------------------------
+# The permutation law (the only place it is written on the host side; ops.permutation_sources runs
+# this function on either device): for seed s and repeat r, row i ∈ [0, n) gets
+#     key = splitmix64(s ^ splitmix64((r << 25) ^ i)) >> 1         (logical shift: 0 ≤ key < 2^63)
+# and src_r = the stable ascending argsort of the keys — a permutation even when two keys collide.
+# One permutation per repeat, shared by every column (a paired design).  Hybrid row (k, r, i) is x[i]
+# with column k replaced by x[src_r[i]][k].  n ≤ 2^25, r < 2^24.
+
+def permutation_sources(n: int, r0: int, r1: int, seed: int = 0, device="cpu", chunk_elems: int = 1 << 22):
+    """``src [r1 − r0, n]`` (int32) of the law above for repeats ``r0:r1``, ``chunk_elems // n`` repeats
+    at a time; repeat r does not depend on the range or the chunk it is computed in."""
+    i64 = torch.int64
+    dev = torch.device(device)
+    i = torch.arange(n, dtype=i64, device=dev)
+    sd = torch.tensor(_seed_i64(seed), dtype=i64, device=dev)
+    out = torch.empty(r1 - r0, n, dtype=torch.int32, device=dev)
+    per = max(1, chunk_elems // max(n, 1))
+    for c0 in range(r0, r1, per):
+        rs = torch.arange(c0, min(r1, c0 + per), dtype=i64, device=dev)
+        key = _splitmix64_t(sd ^ _splitmix64_t((rs[:, None] << 25) ^ i[None, :]))
+        key = (key >> 1) & ((1 << 63) - 1)
+        out[c0 - r0:c0 - r0 + rs.numel()] = torch.argsort(key, dim=1, stable=True).to(torch.int32)
+    return out
+
+
+def stack_permute_scores(x: torch.Tensor, pk, src: torch.Tensor, features: torch.Tensor, chunk: int = 4096):
+    """fp64 mirror of ``ops.stack_permute_scores``: ``S [K, R, n]`` = :func:`stack_infer` of the
+    materialised hybrid rows (``features[kf] = −1``: the rows as they are).  ``x`` is first rounded to
+    f32, as the kernel sees it; ``chunk // n`` repeats are materialised at a time (a few thousand rows per
+    call: :func:`rbf_decision` builds a [rows, SVs, F] f64 tensor, 59 kB per row of the shipped model)."""
+    x = x.to(torch.float32).to(torch.float64)
+    src = src.to(torch.int64)
+    n, F = x.shape
+    R = src.shape[0]
+    S = torch.empty(len(features), R, n, dtype=torch.float64)
+    per = max(1, chunk // n)
+    for kf, k in enumerate(int(v) for v in features):
+        for c0 in range(0, R, per):
+            c1 = min(R, c0 + per)
+            h = x[None, :, :].repeat(c1 - c0, 1, 1)                     # [repeats, n, F]
+            if k >= 0:
+                h[:, :, k] = x[:, k][src[c0:c1]]
+            S[kf, c0:c1] = stack_infer(h.reshape(-1, F), pk).reshape(c1 - c0, n)
+    return S
+
+
+class RankMetrics(_NamedOutputs):
+    """The outputs of ``rank_metrics`` in order, also by name."""
+    _fields = ("a2", "auroc", "ap", "brier")
+
+
+def rank_metrics(y: torch.Tensor, scores: torch.Tensor, chunk_elems: int = 1 << 22):
+    """Torch mirror of the ``rank_rows`` kernel (and the host path of ``ops.rank_metrics``, which
+    validates): every row of ``scores [M, n]`` ranked against the labels ``y [n]``.  ``a2 [M]`` (int64) =
+    the exact doubled AUROC numerator over tie groups, ``auroc`` = ``a2 / (2·P·N)``, ``ap`` = the kernel's
+    tie-group formula and ``brier`` = ``Σ(score − y)² / n`` folded as the kernel folds it (f64).  Ties
+    are equal values of ``scores``' own dtype.  ``chunk_elems // n`` rows at a time."""
+    i64, f64 = torch.int64, torch.float64
+    dev = scores.device
+    M, n = scores.shape
+    yi = (y.to(dev) > 0).to(i64)
+    P = int(yi.sum())
+    N = n - P
+    last = torch.ones(1, dtype=torch.bool, device=dev)
+    outs = [[] for _ in range(4)]
+    per = max(1, chunk_elems // n)
+    for c0 in range(0, M, per):
+        s = scores[c0:c0 + per]
+        m = s.shape[0]
+        ss, order = torch.sort(s, dim=1, descending=True, stable=True)
+        ys = yi[order]
+        cp, cn = torch.cumsum(ys, 1), torch.cumsum(1 - ys, 1)
+        end = torch.cat([ss[:, 1:] != ss[:, :-1], last.expand(m, 1)], 1)
+        # the cumulative counts at the previous group end (both are nondecreasing along the row)
+        z = torch.zeros(m, 1, dtype=i64, device=dev)
+        cp0 = torch.cat([z, torch.cummax(torch.where(end, cp, 0), 1).values[:, :-1]], 1)
+        cn0 = torch.cat([z, torch.cummax(torch.where(end, cn, 0), 1).values[:, :-1]], 1)
+        a2 = torch.where(end, (cn - cn0) * (cp + cp0), 0).sum(1)
+        term = torch.where(end & (cp != cp0), ((cp - cp0) * cp).to(f64) / (cp + cn).to(f64), 0.0)
+        d = s.to(f64) - yi.to(f64)[None, :]
+        nan = float("nan")
+        deg = P == 0 or N == 0
+        outs[0].append(a2)
+        # tensor divisors: torch turns a division by a Python scalar on ``cuda`` into a product with its reciprocal
+        den = torch.tensor([2 * P * N, P, n], dtype=f64, device=dev)
+        outs[1].append(a2.to(f64) / den[0] if not deg else torch.full((m,), nan, dtype=f64, device=dev))
+        outs[2].append(term.sum(1) / den[1] if not deg else torch.full((m,), nan, dtype=f64, device=dev))
+        outs[3].append(_compare_fold(d * d) / den[2])
+    if not outs[0]:
+        return RankMetrics(torch.empty(0, dtype=i64, device=dev), *(torch.empty(0, dtype=f64, device=dev)
+                                                                    for _ in range(3)))
+    return RankMetrics(*(torch.cat(o) for o in outs))
+
+
 def compare_oracle(y, scores, n_boot: int, *, seed: int = 0, stratified: bool = False, threshold: float = 0.5,
                    b0: int = 0, b1=None):
     """Independent oracle for the tests: ``a2``, ``ap`` and ``conf`` of every column come from

@@ -93,11 +93,12 @@ class DevelopResult:
     n_train: int = 0
     bases_sel: Optional[torch.Tensor] = None      # keep_bases: [n_sel, 3] f64 base-learner P(class 1)
     base_names: Optional[List[str]] = None
+    X_sel: Optional[torch.Tensor] = None          # keep_heldout: [n_sel, F] f64 imputed, selected held-out columns
 
 
 def develop(X_dev, y_dev, X_sel, y_sel, names, device="cpu", cfg: Optional[EnsembleConfig] = None,
             timer: Optional[StageTimer] = None, group=None, evaluate: bool = True,
-            keep_bases: bool = False) -> DevelopResult:
+            keep_bases: bool = False, keep_heldout: bool = False) -> DevelopResult:
     cfg = cfg or EnsembleConfig()
     timer = timer or StageTimer(enabled=True, device=device if str(device).startswith("cuda") else None)
     dev = torch.device(device)
@@ -232,4 +233,5 @@ def develop(X_dev, y_dev, X_sel, y_sel, names, device="cpu", cfg: Optional[Ensem
     if fit_group is not None:
         from .parallel import dist as pdist
         n_train = pdist.all_reduce_int(n_train, group)
-    return DevelopResult(clf, mask, fn_new, proba, report, scores, timer, n_train, bases, base_names)
+    return DevelopResult(clf, mask, fn_new, proba, report, scores, timer, n_train, bases, base_names,
+                         X_sel_optm if keep_heldout else None)

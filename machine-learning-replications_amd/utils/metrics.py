@@ -502,6 +502,54 @@ def save_compare_plot(y_true, scores: Dict[str, object], prefix: str) -> str:
     return path
 
 
+def save_importance_plot(imp: Dict[str, object], prefix: str) -> str:
+    """Horizontal bars of the mean AUROC importance of every variable with its interval as whiskers,
+    most important on top, ``<prefix>_importance``; ``imp`` is the CLI's ``"importance"`` record.  PNG
+    through matplotlib when it is installed, otherwise SVG."""
+    rows = list(imp["variables"])
+    names = [r["name"] for r in rows]
+    mean = [r["auroc"]["mean"] for r in rows]
+    lo = [r["auroc"]["lo"] for r in rows]
+    hi = [r["auroc"]["hi"] for r in rows]
+    xlabel = f"fall of AUROC under permutation ({imp['n_repeats']} shuffles)"
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except Exception:
+        x0, x1 = min(0.0, min(lo)), max(max(hi), 1e-12)
+        W, rowh, left, m = 640, 18, 220, 30
+        H = 2 * m + rowh * len(rows)
+
+        def px(v):
+            return left + (float(v) - x0) / (x1 - x0) * (W - left - m)
+        parts = [f'<svg xmlns="http://www.w3.org/2000/svg" width="{W}" height="{H}" font-family="sans-serif" '
+                 f'font-size="11">', f'<rect width="{W}" height="{H}" fill="white"/>',
+                 f'<line x1="{px(0):.1f}" y1="{m}" x2="{px(0):.1f}" y2="{H - m}" stroke="black"/>']
+        for i, name in enumerate(names):
+            yc = m + rowh * i + rowh / 2
+            a, b = sorted((px(0.0), px(mean[i])))
+            parts.append(f'<text x="{left - 6}" y="{yc + 4:.1f}" text-anchor="end">{name}</text>')
+            parts.append(f'<rect x="{a:.1f}" y="{yc - 5:.1f}" width="{b - a:.1f}" height="10" fill="#1f77b4"/>')
+            parts.append(f'<line x1="{px(lo[i]):.1f}" y1="{yc:.1f}" x2="{px(hi[i]):.1f}" y2="{yc:.1f}" stroke="black"/>')
+        parts.append(f'<text x="{(left + W - m) / 2:.1f}" y="{H - 8}" text-anchor="middle">{xlabel}</text></svg>')
+        path = prefix + "_importance.svg"
+        with open(path, "w") as f:
+            f.write("\n".join(parts))
+        return path
+    fig = plt.figure(figsize=(7, max(3.0, 0.3 * len(rows) + 1.0)))
+    pos = list(range(len(rows)))[::-1]
+    err = [[max(0.0, m_ - l) for m_, l in zip(mean, lo)], [max(0.0, h - m_) for m_, h in zip(mean, hi)]]
+    plt.barh(pos, mean, xerr=err, color="#1f77b4", ecolor="black", capsize=2)
+    plt.yticks(pos, names)
+    plt.axvline(0.0, color="black", linewidth=0.8)
+    plt.xlabel(xlabel); plt.grid(True, axis="x"); plt.tight_layout()
+    path = prefix + "_importance.png"
+    fig.savefig(path, dpi=120)
+    plt.close(fig)
+    return path
+
+
 def _svg_plot(path: str, curves, band, points, xlabel: str, ylabel: str, ylim) -> str:
     """The approach of :func:`_svg_curve` for several curves on a y-range that need not be [0, 1]:
     ``curves`` = ``(x, y, colour, dash, label)``, ``band`` = ``(x, lo, hi)`` or None, ``points`` =
