@@ -9,6 +9,10 @@ GBDT training oracles (Python ints, Fractions, longdouble; nothing shared with
 models/hist_gbdt.py): ``gbdt_q``, ``gbdt_hist_oracle``, ``gbdt_split_oracle`` (with
 ``GbdtSplit.certify`` and ``gbdt_split_children``), ``gbdt_bag_oracle``,
 ``gbdt_route_oracle``, ``gbdt_route_r2_oracle``, ``gbdt_apply_prep_oracle``.
+
+Nyström interior-point SVC oracles (numpy longdouble and plain f64; nothing shared with
+models/svc_lowrank.py): ``wgram_oracle``, ``phi_mv_oracle``, ``phit_oracle``, ``rbf_oracle_f64``,
+``chol_certificate``, ``chol_solve_certificate``, ``ipm_rows_oracle``, ``svc_dual_certificate``.
 """
 from __future__ import annotations
 
@@ -2662,3 +2666,382 @@ def gamma_oracle(Z, offs, F):
                 g[f] = np.nan
         ngl2e = (-g * np.log2(np.exp(L(1)))).astype(np.float32)
     return g, ngl2e
+
+
+# ----------------------------------------------------------------------------- Nyström interior-point SVC oracles
+# numpy only, written from the headers of ops/csrc/lowrank.hip, linalg.hip and nystrom.hip (what each
+# kernel is documented to compute), from Higham, "Accuracy and Stability of Numerical Algorithms"
+# (2002; §3.1 sums in any order, Theorem 10.3 Cholesky, Theorem 8.5 substitution) and from the C-SVC
+# dual itself.  longdouble where a value is compared, plain f64 in the kernel's own operation order
+# where bits are compared.  Nothing here imports torch.linalg or models/svc_lowrank.py.
+#
+# Notation: u = 2⁻⁵³ (LR_U), γ_k = k·u/(1 − k·u) (lr_gamma); γ32_k the same with 2⁻²⁴.  Every bound is
+# per entry and relative to the magnitude of that entry's own terms, so one wrong small entry cannot
+# hide behind a large one.
+LR_U = 2.0 ** -53
+LR_U32 = 2.0 ** -24
+LR_WF_FLUSH = 256               # lowrank.hip kWfFlush: rows per f32 accumulation of wsyrk_f32
+LR_EXP_ULP = 2                  # assumed error of the device's double exp, in ulp (profiles/lowrank_oracles.md)
+LR_JIT0 = 1e-14                 # linalg.hip: the jitter ladder 1e-14, ×100 per retry, up to 1
+LR_IPM_TOL = 1e-8               # models/svc_lowrank.py IPM_TOL (gap) and the tight residual / equality rule
+LR_RD_LOOSE = 1e-5              # models/svc_lowrank.py RD_LOOSE
+LR_SNAP = 1e-9                  # the final snap of α onto a bound it is within 1e-9·c of
+
+
+def lr_gamma(k, u=LR_U):
+    """γ_k = k·u/(1 − k·u), longdouble."""
+    L = _np().longdouble
+    return L(k) * L(u) / (1 - L(k) * L(u))
+
+
+def wgram_oracle(Phi, d):
+    """``(S, M)`` longdouble [r, r]: S = Φᵀ diag(d) Φ and M = |Φ|ᵀ diag(|d|) |Φ|.
+
+    f64 kernels (wsyrk_f64, wsyrk_f64x): each term is fl(d_i·φ_ij)·φ_ik — one rounding — entering an
+    fma accumulation (no product rounding); the n terms of an entry are then summed in SOME order
+    (16- or 32-row slabs, 4 rows per MFMA, row groups, the group-order reduction), and a sum of n
+    terms in any order puts at most n − 1 roundings on a term (Higham §3.1).  So
+    |Ŝ − S| ≤ γ_{n+2}·M (:func:`wgram_bound_f64`; n + 2 ≥ 1 + (n − 1), the slack is Higham's)."""
+    np = _np()
+    P, dd = _ld(Phi), _ld(d)
+    # (row-major transposes: numpy's longdouble product is a plain loop, fastest over contiguous rows)
+    Pt = np.ascontiguousarray(P.T)
+    S = np.ascontiguousarray((P * dd[:, None]).T) @ Pt.T
+    aPt = np.abs(Pt)
+    M = (aPt * np.abs(dd)[None, :]) @ aPt.T
+    return S, M
+
+
+def wgram_bound_f64(M, n):
+    return lr_gamma(n + 2) * M
+
+
+def wgram_bound_f32(M, n):
+    """wsyrk_f32's bound from its own arithmetic.  Φ is exactly f32.  A term d_i·φ_ij is formed in
+    f64 (u) and rounded to f32 (2⁻²⁴); its product with the exact φ_ik and the f32 accumulation over
+    at most F = min(n, kWfFlush) rows put at most 1 + (F − 1) more f32 roundings on it, so within a
+    flush (1 + 2⁻²⁴)^(F+1) ≤ 1 + γ32_{F+2} covers them together with the f64 rounding of d·φ.  The
+    flushed f32 sums are exact in f64 and are added in f64: ⌈n/F⌉ flushes over the row groups plus
+    the group-order reduction, at most n − 1 f64 additions on a term.  Hence
+
+        |Ŝ − S| ≤ ((1 + γ32_{F+2})·(1 + γ_{n+2}) − 1)·M,   F = min(n, 256):
+
+    1.5e-5·M at n ≥ 256 and 1.8e-7·M at n = 1 (f32 range assumed: no term under- or overflows)."""
+    F = min(int(n), LR_WF_FLUSH)
+    return ((1 + lr_gamma(F + 2, LR_U32)) * (1 + lr_gamma(n + 2)) - 1) * M
+
+
+def phi_mv_oracle(Phi, W):
+    """``(Y, Ymag)`` longdouble [n, k]: Y = Φ W and |Φ||W|.  phi_gemv / phi_gemv_f32 sum r fma terms
+    in some order (8 per lane, then a wave sum): |Ŷ − Y| ≤ γ_{r+1}·Ymag."""
+    np = _np()
+    P, Wl = _ld(Phi), _ld(W)
+    return P @ Wl, np.abs(P) @ np.abs(Wl)
+
+
+def phit_oracle(Phi, V):
+    """``(O, Omag)`` longdouble [r, k]: O = Φᵀ V and |Φ|ᵀ|V|.  phit_f32 sums n fma terms in some order
+    (per thread, per workgroup in LDS, the slot-order reduction): |Ô − O| ≤ γ_{n+1}·Omag."""
+    np = _np()
+    P, Vl = _ld(Phi), _ld(V)
+    return P.T @ Vl, np.abs(P).T @ np.abs(Vl)
+
+
+def rbf_oracle_f64(A, B, gamma):
+    """``(K, dK)`` longdouble [l, m]: K = exp(−γ‖a − b‖²) with d² summed from the differences, and the
+    forward bound of rbf_f64's evaluation  t = fl(a_f − b_f); d̂ = fma(t, t, d̂) over f < F;
+    K̂ = exp(fl(−γ·d̂)).
+
+    * every t carries one rounding (twice in t²) and the F-step fma chain at most F more on a term:
+      d̂ = d²(1 + θ), |θ| ≤ γ_{F+2} (all terms non-negative: no cancellation);
+    * fl(−γ·d̂) rounds once more: the exponent is off by δ ≤ γ_{F+2}·γd² + u·γd²(1 + γ_{F+2});
+    * exp itself: K̂ = e^x̂(1 + ε), |ε| ≤ E = LR_EXP_ULP·2u (one ulp is at most 2u of the value);
+    * a result below the normal range is a subnormal or a flushed 0: 2⁻¹⁰²² absolute there.
+
+    dK = K·((e^δ − 1)(1 + E) + E)  (+ 2⁻¹⁰²² where K < 2⁻¹⁰²¹)."""
+    np = _np()
+    L = np.longdouble
+    A, B = _ld(A), _ld(B)
+    F = A.shape[1]
+    g = L(gamma)
+    d2 = np.zeros((A.shape[0], B.shape[0]), dtype=L)
+    for f in range(F):
+        t = A[:, f][:, None] - B[:, f][None, :]
+        d2 += t * t
+    gF = lr_gamma(F + 2)
+    with np.errstate(under="ignore"):
+        K = np.exp(-g * d2)
+        delta = gF * g * d2 + L(LR_U) * g * d2 * (1 + gF)
+        E = L(LR_EXP_ULP) * 2 * L(LR_U)
+        dK = K * (np.expm1(delta) * (1 + E) + E)
+    dK = dK + np.where(K < L(2.0) ** -1021, L(2.0) ** -1022, 0)
+    return K, dK
+
+
+class Certificate:
+    """A certificate's verdict: ``ok``, ``why`` (the conditions that failed) and ``worst`` (per
+    condition, the largest observed error as a fraction of its bound; ≤ 1 passes)."""
+    __slots__ = ("ok", "why", "worst", "extra")
+
+    def __init__(self):
+        self.ok, self.why, self.worst, self.extra = True, [], {}, {}
+
+    def check(self, name, err, bound):
+        """``err ≤ bound`` everywhere (arrays or scalars; a NaN fails)."""
+        np = _np()
+        err, bound = np.asarray(err, dtype=np.longdouble), np.asarray(bound, dtype=np.longdouble)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(err == 0, 0, err / bound)
+        w = float(np.max(ratio)) if ratio.size else 0.0
+        self.worst[name] = w
+        if not (np.all(err <= bound) and np.isfinite(err).all()):
+            self.fail(name)
+
+    def fail(self, name):
+        self.ok = False
+        self.why.append(name)
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return f"Certificate(ok={self.ok}, why={self.why}, worst={self.worst})"
+
+
+def entries_within(name, got, want, bound, cert=None):
+    """|got − want| ≤ bound per entry, as a :class:`Certificate` (got f64, want / bound longdouble)."""
+    np = _np()
+    cert = cert or Certificate()
+    cert.check(name, np.abs(_ld(got) - want), bound)
+    return cert
+
+
+def chol_jitter(info):
+    """The diagonal shift of retry ``info`` of linalg.hip's ladder: 0, then 1e-14·100^(info − 1),
+    formed as the kernel forms it (×100.0 in f64 per retry)."""
+    if info <= 0:
+        return 0.0
+    j = LR_JIT0
+    for _ in range(int(info) - 1):
+        j = j * 100.0
+    return j
+
+
+def chol_certificate(S, L, sc, info):
+    """Higham's certificate of chol_spd / chol_spd_mw, in longdouble, from the outputs alone:
+
+    * ``sc``: sc_i = diag(S)_i^-½ to one ulp.  The kernel takes a square root and a reciprocal,
+      each correctly rounded: (1 + u)/(1 − u) − 1 ≤ γ_2 = 2⁻⁵²(1 + …), one ulp at the low end of a
+      binade, which is what is required (sc_i = 1 where S_ii ≤ 0);
+    * ``factor``: |L Lᵀ − (sc·S·sc + jit(info)·I)| ≤ γ_{r+1}·|L||Lᵀ| per entry (Theorem 10.3), with the
+      kernel's own sc and :func:`chol_jitter`;
+    * ``diag``: L_ii > 0;  ``upper``: the strict upper triangle is exactly 0;  ``info``: 0 ≤ info ≤ 8."""
+    np = _np()
+    Ll = np.longdouble
+    cert = Certificate()
+    S0, L0 = np.asarray(S, dtype=np.float64), np.asarray(L, dtype=np.float64)
+    r = S0.shape[0]
+    Sl, Lf, scl = _ld(S0), _ld(L0), _ld(sc)
+    if not (0 <= int(info) <= 8):
+        cert.fail("info")
+        return cert
+    dg = np.diagonal(Sl)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        want = np.where(dg > 0, 1 / np.sqrt(np.where(dg > 0, dg, 1)), Ll(1))
+    cert.check("sc", np.abs(scl - want), lr_gamma(2) * np.abs(want))
+    T = Sl * scl[:, None] * scl[None, :] + Ll(chol_jitter(info)) * np.eye(r, dtype=Ll)
+    # the lower triangle (the part of S the kernel reads), the products taken over column blocks of the
+    # lower-triangular factor: a third of the full product's work, the same sums
+    Lt = np.tril(Lf)
+    LLt, mag = np.zeros((r, r), dtype=Ll), np.zeros((r, r), dtype=Ll)
+    for k0 in range(0, r, 64):
+        blk = Lt[k0:, k0:k0 + 64]
+        LLt[k0:, k0:] += blk @ blk.T
+        mag[k0:, k0:] += np.abs(blk) @ np.abs(blk).T
+    low = np.tril(np.ones((r, r), dtype=bool))
+    cert.check("factor", np.abs(LLt - T)[low], (lr_gamma(r + 1) * mag)[low])
+    if not (np.diagonal(L0) > 0).all():
+        cert.fail("diag")
+    if np.triu(L0, 1).any() or np.isnan(L0).any():
+        cert.fail("upper")
+    return cert
+
+
+def chol_solve_certificate(L, sc, B, X):
+    """Componentwise backward error of chol_solve's two substitutions, per right-hand side: with
+    Y = X/sc,  |(L Lᵀ)Y − sc·B| ≤ γ_{3r+1}·|L||Lᵀ||Y|  per entry (Theorem 8.5 twice: (L + ΔL)(L + ΔL')ᵀ
+    with |ΔL| ≤ γ_r|L| gives 2γ_r + γ_r² ≤ γ_{2r+1}; the remaining r cover the two scalings by sc and
+    the reciprocal pivots)."""
+    np = _np()
+    cert = Certificate()
+    Lf, scl, Bl, Xl = _ld(L), _ld(sc), _ld(B), _ld(X)
+    r = Lf.shape[0]
+    Y = Xl / scl[:, None]
+    res = np.abs(Lf @ (Lf.T @ Y) - scl[:, None] * Bl)
+    bound = lr_gamma(3 * r + 1) * (np.abs(Lf) @ (np.abs(Lf).T @ np.abs(Y)))
+    for q in range(Bl.shape[1]):
+        cert.check(f"rhs{q}", res[:, q], bound[:, q])
+    return cert
+
+
+class ipm_rows_oracle:
+    """One plain numpy f64 function per row kernel of lowrank.hip: the operations and their
+    parenthesisation are the kernel comments' (numpy neither contracts nor reorders), so outputs
+    are compared bit for bit.  Vectors are f64 [n]; device scalars are Python floats; ``Mh`` / ``My``
+    / ``P`` are the already strided columns."""
+
+    @staticmethod
+    def resid(c, a, y, P, b, nu, mu):
+        """s = c − α,  rd = ((y·P − 1) + b·y − ν) + μ."""
+        g = y * P - 1.0
+        return c - a, ((g + b * y) - nu) + mu
+
+    @staticmethod
+    def pred(a, s, nu, mu, rd, y):
+        """D⁻¹ = 1/(ν/α + μ/s), its two-column copy, rν = α·ν, rμ = s·μ, H2 = [((−rd) − rν/α) + rμ/s, y]."""
+        np = _np()
+        di = 1.0 / (nu / a + mu / s)
+        rn, rm = a * nu, s * mu
+        h = (-rd - rn / a) + rm / s
+        return di, np.stack([di, di], 1), rn, rm, np.stack([h, y], 1)
+
+    @staticmethod
+    def corr(a, s, nu, mu, da, dnu, dmu, rd, tau):
+        """rν = (α·ν + Δα·Δν) − τ,  rμ = (s·μ − Δα·Δμ) − τ,  h = ((−rd) − rν/α) + rμ/s."""
+        rn = (a * nu + da * dnu) - tau
+        rm = (s * mu - da * dmu) - tau
+        return rn, rm, (-rd - rn / a) + rm / s
+
+    @staticmethod
+    def dirs(Mh, My, db, rnu, rmu, nu, mu, a, s):
+        """Δα = Mh − db·My,  Δν = (−rν − ν·Δα)/α,  Δμ = (−rμ + μ·Δα)/s."""
+        d = Mh - db * My
+        return d, (-rnu - nu * d) / a, (-rmu + mu * d) / s
+
+    @staticmethod
+    def minv_pre(Dinv, y, U):
+        """du = D⁻¹ ∘ U,  V = y ∘ du  (U [n, k])."""
+        du = Dinv[:, None] * U
+        return du, y[:, None] * du
+
+    @staticmethod
+    def minv_post(Dinv, y, du, P):
+        """out = du − D⁻¹ ∘ (y ∘ P)."""
+        return du - Dinv[:, None] * (y[:, None] * P)
+
+    @staticmethod
+    def update(a, nu, mu, da, dnu, dmu, t):
+        return a + t * da, nu + t * dnu, mu + t * dmu
+
+    @staticmethod
+    def gondzio_rhs(a, s, nu, mu, da, dnu, dmu, alpha, tau):
+        """α̃ = min(1.5α + 0.1, 1); the trial products pushed into [0.1τ, 10τ], floored at −10τ."""
+        np = _np()
+        at = min(1.5 * alpha + 0.1, 1.0)
+        lo, hi = 0.1 * tau, 10.0 * tau
+        va = (a + at * da) * (nu + at * dnu)
+        vs = (s - at * da) * (mu + at * dmu)
+        tca = np.maximum(np.minimum(np.maximum(va, lo), hi) - va, -hi)
+        tcs = np.maximum(np.minimum(np.maximum(vs, lo), hi) - vs, -hi)
+        return tca, tcs, tca / a - tcs / s
+
+    @staticmethod
+    def gondzio_apply(Mh, My, dbc, da, dnu, dmu, ta, ts, nu, mu, a, s):
+        dac = Mh - dbc * My
+        return da + dac, dnu + (ta - nu * dac) / a, dmu + (ts + mu * dac) / s
+
+    @staticmethod
+    def select3(ok, x, y):
+        """The three ``x`` where the flag is set, else the three ``y`` untouched."""
+        return tuple(v.copy() for v in (x if ok else y))
+
+    @staticmethod
+    def max_step(pairs, signs):
+        """min(1, min over the pairs (v, dv) and rows with sign·dv < 0 of −v/(sign·dv)): the IEEE
+        quotient, and a minimum is exact in any order."""
+        np = _np()
+        m = 1.0
+        for (v, dv), sg in zip(pairs, signs):
+            a = sg * dv
+            neg = a < 0.0
+            if neg.any():
+                m = min(m, float(np.min(-v[neg] / a[neg])))
+        return m
+
+    @staticmethod
+    def fill(n, src):
+        return _np().full(int(n), src, dtype=_np().float64)
+
+    @staticmethod
+    def scale_rows(P32, d):
+        """diag(d)·Φ from the f32 copy: one f64 product per entry."""
+        np = _np()
+        return np.asarray(P32, dtype=np.float32).astype(np.float64) * np.asarray(d, dtype=np.float64)[:, None]
+
+
+def svc_dual_certificate(Phi, y, c, alpha, rho, rd_tol=LR_RD_LOOSE):
+    """KKT certificate of the C-SVC dual  min ½αᵀQα − 1ᵀα, yᵀα = 0, 0 ≤ α ≤ c,  Q = diag(y)ΦΦᵀdiag(y),
+    in longdouble, from (α, ρ) alone.  rank(Q) ≤ r, so α is not unique: what is certified is
+    w = Φᵀ(y∘α), ρ and the objective.
+
+    The solver's stopping rule (models/svc_lowrank.py ``_ipm_gen``), with b = −ρ, s = c − α,
+    multipliers ν, μ ≥ 0 and rd = (y∘Φw − 1) + b·y − ν + μ, is
+
+        (αᵀν + sᵀμ)/(2l) < IPM_TOL,   max|rd| < 1e-8 (or < RD_LOOSE once the gap has converged),
+        |yᵀα| < 1e-8·Σc,
+
+    after which α within 1e-9·c of a bound is snapped onto it.  ν and μ are not returned, so the rule
+    is restated in (w, ρ): with q = y∘(Φw + b) − 1 the multipliers of least residual are
+    ν* = max(q, 0), μ* = max(−q, 0) (these are the hinge slacks ξ = μ* of the primal at (w, ρ)), and
+    any ν, μ ≥ 0 with |q − ν + μ| ≤ ε have ν ≥ ν* − ε, μ ≥ μ* − ε, so
+    αᵀν* + sᵀμ* ≤ αᵀν + sᵀμ + ε·Σc.  The left side minus b·yᵀα is exactly the duality gap
+    P(w, ρ) − D(α), P = ½‖w‖² + Σ c_i ξ_i, D = Σα − ½‖w‖².  Conditions:
+
+    * ``box``: 0 ≤ α ≤ c exactly;
+    * ``eq``: |yᵀα| ≤ (1e-8 + 1e-9)·Σc (the rule plus the snap of every point);
+    * ``gap``: P − D ≤ 2l·IPM_TOL + rd_tol·Σc + |b|·eq + snap + rounding, where
+      - snap: the snap moves α_i by ≤ 1e-9·c_i on points now at a bound, so w by
+        ≤ δw = 1e-9·Σ_{at a bound} c_i‖φ_i‖ and q_i by ≤ dq_i = ‖φ_i‖·δw.  The gap is a sum of
+        f_i(q_i, α_i) = α_i·max(q_i, 0) + s_i·max(−q_i, 0) − b·y_i·α_i, which does not change at a point
+        that is at 0 with q_i > dq_i or at c_i with q_i < −dq_i, and changes by ≤ c_i·dq_i elsewhere;
+        the move of α_i itself adds ≤ 1e-9·c_i·(|q_i| + dq_i + |b|) at the points at a bound;
+      - rounding: the solver evaluates rd in f64: γ_{l+r+8}·Σc·max_i(|φ_i|·|Φ|ᵀα + 1 + |b|).
+
+    ``extra`` holds w, P, D, gap, gap_bound, the relative gap (P − D)/(1 + |D|) and max|rd*|, the
+    residual left when ν*, μ* are restricted by complementarity (informative).  Since D ≤ D* = P* ≤ P
+    and P is ½-strongly convex in w, a certified gap also bounds |D − D*| ≤ gap and
+    ‖w − w*‖ ≤ √(2·gap)."""
+    np = _np()
+    L = np.longdouble
+    cert = Certificate()
+    P, yl, cl, al = _ld(Phi), _ld(y), _ld(c), _ld(alpha)
+    l, r = P.shape
+    b = -L(rho)
+    csum = cl.sum()
+    if not ((al >= 0).all() and (al <= cl).all()):
+        cert.fail("box")
+    eq_bound = (L(LR_IPM_TOL) + L(LR_SNAP)) * csum
+    ya = yl @ al
+    cert.check("eq", np.abs(ya), eq_bound)
+    w = P.T @ (yl * al)
+    q = yl * (P @ w + b) - 1
+    nus, mus = np.maximum(q, 0), np.maximum(-q, 0)
+    s = cl - al
+    Pobj = (w @ w) / 2 + (cl * mus).sum()
+    Dobj = al.sum() - (w @ w) / 2
+    gap = Pobj - Dobj
+    nphi = np.sqrt((P * P).sum(1))
+    atb = (al == 0) | (al == cl)
+    dw = L(LR_SNAP) * (cl * nphi)[atb].sum()
+    dq = nphi * dw
+    safe = ((al == 0) & (q > dq)) | ((al == cl) & (q < -dq))
+    snap = (cl * dq)[~safe].sum() + L(LR_SNAP) * (cl * (np.abs(q) + dq + np.abs(b)))[atb].sum()
+    mag = (np.abs(P) @ (np.abs(P).T @ al) + 1 + np.abs(b)).max() if l else L(0)
+    rounding = lr_gamma(l + r + 8) * csum * mag
+    gap_bound = 2 * l * L(LR_IPM_TOL) + L(rd_tol) * csum + np.abs(b) * eq_bound + snap + rounding
+    cert.check("gap", gap, gap_bound)
+    cert.extra = {"w": w, "rho": -b, "P": Pobj, "D": Dobj, "gap": gap, "gap_bound": gap_bound, "snap": snap,
+                  "rel_gap": gap / (1 + np.abs(Dobj)),
+                  "rd": np.abs(np.where(al == 0, np.minimum(q, 0), np.where(al == cl, np.maximum(q, 0), q))).max()
+                  if l else L(0)}
+    return cert
